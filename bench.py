@@ -6,8 +6,14 @@ BiLSTM + CRF, the BASELINE.json headline config) on MSRA-shaped
 synthetic data, bf16, random-init weights. Weak scaling: per-GPU batch
 fixed; `value` is the whole-job aggregate samples/sec.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1 is launched by the driver via torch.distributed.run, one rank/GPU)
+
+A plain run sets up, warms up, times the K steps and prints one JSON
+line. --dump-outputs DIR additionally writes the last timed step's
+results as DIR/*.npy (inputs are seeded, so two builds can be compared
+output for output). --full is where any measurement beyond the headline
+figure belongs; there is none today.
 """
 from __future__ import annotations
 
@@ -45,6 +51,34 @@ from chinesener_amd.models import build_model, model_params, optimizer_family
 from chinesener_amd.train.optimizers import build_optimizer, clip_gradients
 
 
+DUMP_PER_PARAM = 4096   # elements sampled from each parameter tensor
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write what the last timed training step produced: its loss, and
+    the parameters it updated. A BERT-base parameter set is ~440 MB in
+    fp32, so each tensor contributes a fixed, seeded sample of at most
+    DUMP_PER_PARAM elements (~3 MB in all), concatenated in
+    named_parameters() order. The sample indices depend only on the
+    parameter shapes, so two builds are comparable element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().cpu().numpy().reshape(-1))
+    gen = torch.Generator().manual_seed(20240531)
+    chunks = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_PER_PARAM:
+                idx = torch.randint(flat.numel(), (DUMP_PER_PARAM,),
+                                    generator=gen)
+                flat = flat[idx.to(flat.device)]
+            chunks.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(chunks).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -54,6 +88,15 @@ def main():
                     help="per-GPU batch (weak scaling; global=batch*gpus)")
     ap.add_argument("--seq_len", type=int, default=128)
     ap.add_argument("--model", default="bert_bilstm_crf")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step produced (loss + a fixed seeded sample of "
+                         "the updated parameters) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure (none today: a plain run already "
+                         "does only setup, warmup, the timed steps and the "
+                         "result line)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -228,8 +271,9 @@ def main():
     if use_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_loss = None
     for i in range(args.steps):
-        train_step(batches[i % len(batches)])
+        last_loss = train_step(batches[i % len(batches)])
     if dist is not None:
         dist.barrier()
     if use_gpu:
@@ -242,6 +286,8 @@ def main():
         elapsed = float(t.item())
 
     if rank == 0:
+        if args.dump_outputs and last_loss is not None:
+            dump_outputs(args.dump_outputs, last_loss, model)
         total_samples = args.steps * args.batch_size * world
         result = {
             "metric": f"training samples/sec, {args.model} (BERT-base + BiLSTM + CRF), msra-shaped"

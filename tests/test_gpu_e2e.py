@@ -260,7 +260,7 @@ def test_every_model_trains_on_gpu(model_name):
 
 
 @pytest.mark.gpu
-def test_device_prefetcher_gpu():
+def test_device_prefetcher_gpu(tmp_path):
     """Pinned side-stream H2D staging delivers every batch, on-device,
     bit-identical, in order. Ring-buffer contract (allocation-free
     replay loops): a handed-out batch is valid until the NEXT two
@@ -292,7 +292,7 @@ def test_device_prefetcher_gpu():
     from chinesener_amd.models import build_model
     params = make_tiny_params("bilstm_crf")
     model = build_model("bilstm_crf", params)
-    tr = Trainer(model, "bilstm_crf", params, "/tmp/prefetch_ck",
+    tr = Trainer(model, "bilstm_crf", params, str(tmp_path / "prefetch_ck"),
                  device="cuda:0")
     batches = [make_tiny_batch("bilstm_crf", batch_size=2, seed=i)
                for i in range(6)]

@@ -363,3 +363,42 @@ def test_bench_json_driver_contract():
     assert r["config"]["parallelism"] == "dp1"
     # value is the whole-job aggregate: steps*batch/elapsed
     assert abs(r["value"] - 2 * 2 / (r["ms_per_step"] * 2 / 1000)) < 1.0
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss and parameter
+    sample as float32 .npy; the same arguments give the same inputs, so
+    on CPU (deterministic fp32 kernels) two runs agree bit for bit.
+    --full is accepted and leaves the result line's contract intact."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # pin the child to the CPU path: GPU reductions use atomics, so only
+    # the CPU run is bitwise repeatable
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+
+    def run(tag, *extra):
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+             "--warmup", "0", "--batch_size", "1", "--seq_len", "16",
+             "--dump-outputs", str(tmp_path / tag), *extra],
+            capture_output=True, text=True, timeout=600, cwd=repo, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = json.loads(out.stdout.strip().splitlines()[-1])
+        assert r["steps"] == 2 and r["ms_per_step"] > 0
+        assert r["dtype"] == "fp32"          # the CPU path really ran
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == ["loss.npy", "params_sample.npy"], files
+        return {f: np.load(tmp_path / tag / f) for f in files}
+
+    a, b = run("a"), run("b", "--full")
+    total = 0
+    for name, arr in a.items():
+        assert arr.dtype == np.float32, (name, arr.dtype)
+        assert arr.size > 0 and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, b[name]), name
+        total += arr.nbytes
+    assert a["loss.npy"].shape == (1,)
+    assert total <= 64 * 2 ** 20
