@@ -87,9 +87,8 @@ class _DropoutAddLNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         s, weight, mask, mean, rstd = ctx.saved_tensors
-        dsum, dw, db = get_ext().layernorm_bwd(dy.contiguous(), s, weight,
-                                               mean, rstd)
-        dx = get_ext().mask_scale(dsum, mask, 1.0 / ctx.keep)
+        dsum, dx, dw, db, _ = get_ext().dropout_add_ln_bwd(
+            dy.contiguous(), s, weight, mean, rstd, mask, ctx.keep, False)
         return dx, dsum, dw, db, None, None
 
 
@@ -196,12 +195,12 @@ def _pick2(key, fn_ours, fn_lib) -> bool:
     return _GEMM_NT_CHOICE[key]
 
 
-def _pick_gemm_nt(x2, w, bf) -> bool:
+def _pick_gemm_nt(x2, w, b) -> bool:
     """Measured dispatch: first time a (M,N,K,bias) shape shows up, time
     both paths (median of 5 after warmup) and cache the winner. The
     hand-written kernel carries every shape it wins on; hipBLASLt keeps
     the rest (scripts/bench_gemm_nt.py has the per-shape table)."""
-    key = (x2.shape[0], w.shape[0], w.shape[1], bf is not None)
+    key = (x2.shape[0], w.shape[0], w.shape[1], b is not None)
     hit = _GEMM_NT_CHOICE.get(key)
     if hit is not None:
         return hit
@@ -213,9 +212,8 @@ def _pick_gemm_nt(x2, w, bf) -> bool:
         return False
     ext = get_ext()
 
-    bb = bf.to(torch.bfloat16) if bf is not None else None
-    t_ours = _med_time(lambda: ext.gemm_nt(x2, w, bf, False))
-    t_lib = _med_time(lambda: F.linear(x2, w, bb))
+    t_ours = _med_time(lambda: ext.gemm_nt(x2, w, b, False))
+    t_lib = _med_time(lambda: F.linear(x2, w, b))
     _GEMM_NT_CHOICE[key] = bool(t_ours <= t_lib)
     if os.environ.get("CHINESENER_GEMM_DEBUG") == "1":
         import sys
@@ -226,6 +224,68 @@ def _pick_gemm_nt(x2, w, bf) -> bool:
     return _GEMM_NT_CHOICE[key]
 
 
+def _linear_fwd(x, w, b):
+    """y = x @ w^T + b with the measured forward dispatch; the in-tree
+    kernel reads the bias in its stored dtype."""
+    mode = _gemm_nt_mode()
+    if mode != "off":
+        x2 = x.reshape(-1, x.shape[-1])
+        if _gemm_nt_ok(x2, w):
+            x2 = x2.contiguous()
+            wc = w.contiguous()
+            if mode == "force" or _pick_gemm_nt(x2, wc, b):
+                y = get_ext().gemm_nt(x2, wc, b, False)
+                return y.reshape(*x.shape[:-1], w.shape[0])
+    return F.linear(x, w, b)
+
+
+def _linear_dgrad(dyf, x, w):
+    """dx = dy @ w, shaped like x. dyf: contiguous [M, N]."""
+    M, N = dyf.shape
+    K = x.shape[-1]
+    mode = _gemm_nt_mode()
+    bf16 = dyf.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+
+    # dx[M,K] = dy @ w == gemm_nt(dy[M,N], w^T[K,N]) — the transpose of
+    # the small weight (few MB) is part of the timed candidate, so the
+    # measured dispatch accounts for it
+    def dx_ours():
+        return get_ext().gemm_nt(dyf, w.t().contiguous(), None, False)
+
+    def dx_lib():
+        return dyf @ w.to(dyf.dtype)
+
+    if (mode != "off" and bf16 and M % 128 == 0 and K % 128 == 0
+            and N % 64 == 0
+            and (mode == "force"
+                 or _pick2(("dx", M, N, K), dx_ours, dx_lib))):
+        return dx_ours().reshape(x.shape)
+    return dx_lib().reshape(x.shape)
+
+
+def _linear_wgrad(dyf, x, w):
+    """dW[N,K] = dy^T @ x == gemm_nt(dy^T[N,M], x^T[K,M]), in w's dtype."""
+    M, N = dyf.shape
+    K = x.shape[-1]
+    x2 = x.reshape(-1, K)
+    mode = _gemm_nt_mode()
+    bf16 = dyf.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+
+    def dw_ours():
+        return get_ext().gemm_nt(dyf.t().contiguous(),
+                                 x2.t().contiguous(), None, False)
+
+    def dw_lib():
+        return dyf.T @ x2
+
+    if (mode != "off" and bf16 and N % 128 == 0 and K % 128 == 0
+            and M % 64 == 0
+            and (mode == "force"
+                 or _pick2(("dw", M, N, K), dw_ours, dw_lib))):
+        return dw_ours().to(w.dtype)
+    return dw_lib().to(w.dtype)
+
+
 class _LinearFn(torch.autograd.Function):
     """nn.Linear math with a custom column-sum bias grad (torch's generic
     reduce is ~4.5x off memory-bound for [tokens, features] dbias)."""
@@ -234,61 +294,14 @@ class _LinearFn(torch.autograd.Function):
     def forward(ctx, x, w, b):
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
-        mode = _gemm_nt_mode()
-        if mode != "off":
-            x2 = x.reshape(-1, x.shape[-1])
-            if _gemm_nt_ok(x2, w):
-                x2 = x2.contiguous()
-                wc = w.contiguous()
-                bf = b.float() if b is not None else None
-                if mode == "force" or _pick_gemm_nt(x2, wc, bf):
-                    y = get_ext().gemm_nt(x2, wc, bf, False)
-                    return y.reshape(*x.shape[:-1], w.shape[0])
-        return F.linear(x, w, b)
+        return _linear_fwd(x, w, b)
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        K = x.shape[-1]
-        N = w.shape[0]
-        dyf = dy.reshape(-1, N).contiguous()
-        x2 = x.reshape(-1, K)
-        M = dyf.shape[0]
-        mode = _gemm_nt_mode()
-        bf16 = dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-
-        # dgrad: dx[M,K] = dy @ w == gemm_nt(dy[M,N], w^T[K,N]) — the
-        # transpose of the small weight (few MB) is part of the timed
-        # candidate, so the measured dispatch accounts for it
-        def dx_ours():
-            return get_ext().gemm_nt(dyf, w.t().contiguous(), None, False)
-
-        def dx_lib():
-            return dyf @ w.to(dy.dtype)
-
-        if (mode != "off" and bf16 and M % 128 == 0 and K % 128 == 0
-                and N % 64 == 0
-                and (mode == "force"
-                     or _pick2(("dx", M, N, K), dx_ours, dx_lib))):
-            dx = dx_ours().reshape(x.shape)
-        else:
-            dx = dx_lib().reshape(x.shape)
-
-        # wgrad: dW[N,K] = dy^T @ x == gemm_nt(dy^T[N,M], x^T[K,M])
-        def dw_ours():
-            return get_ext().gemm_nt(dyf.t().contiguous(),
-                                     x2.t().contiguous(), None, False)
-
-        def dw_lib():
-            return dyf.T @ x2
-
-        if (mode != "off" and bf16 and N % 128 == 0 and K % 128 == 0
-                and M % 64 == 0
-                and (mode == "force"
-                     or _pick2(("dw", M, N, K), dw_ours, dw_lib))):
-            dw = dw_ours().to(w.dtype)
-        else:
-            dw = dw_lib().to(w.dtype)
+        dyf = dy.reshape(-1, w.shape[0]).contiguous()
+        dx = _linear_dgrad(dyf, x, w)
+        dw = _linear_wgrad(dyf, x, w)
         db = get_ext().colsum(dyf) if ctx.has_bias else None
         return dx, dw, db
 
@@ -304,6 +317,54 @@ def linear(x, weight, bias=None):
         return _LinearFn.apply(x, weight,
                                bias.to(x.dtype) if bias is not None else None)
     return F.linear(x, weight, bias)
+
+
+class _LinearDropoutAddLNFn(torch.autograd.Function):
+    """LayerNorm(dropout(x @ w^T + b) + residual) as one node: the LN
+    backward kernel also emits dx_drop and its column sum, which is the
+    linear's bias grad, so backward needs no mask_scale and no colsum."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, res, ln_w, ln_b, eps, keep):
+        a = _linear_fwd(x, w, b)
+        y, s, mask, mean, rstd = get_ext().dropout_add_ln_fwd(
+            a.reshape(-1, a.shape[-1]).contiguous(), res, ln_w, ln_b, eps,
+            keep, _rng_counter_for(x.device))
+        ctx.save_for_backward(x, w, s, ln_w, mask, mean, rstd)
+        ctx.keep = keep
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, s, ln_w, mask, mean, rstd = ctx.saved_tensors
+        dsum, dx_drop, dw_ln, db_ln, dbias = get_ext().dropout_add_ln_bwd(
+            dy.contiguous(), s, ln_w, mean, rstd, mask, ctx.keep,
+            ctx.has_bias)
+        dx = _linear_dgrad(dx_drop, x, w)
+        dw = _linear_wgrad(dx_drop, x, w)
+        return dx, dw, dbias, dsum, dw_ln, db_ln, None, None
+
+
+def linear_dropout_add_layernorm(x, weight, bias, residual, ln_w, ln_b,
+                                 eps: float = 1e-12, p: float = 0.1,
+                                 training: bool = True):
+    """LayerNorm(dropout(linear(x)) + residual): the BERT sublayer tail.
+    Same GEMM dispatch, same kernels forward and one RNG counter bump as
+    the composition below; the fused node only shortens backward."""
+    if (training and p > 0 and hip_enabled(x) and x.dtype == torch.bfloat16
+            and weight.dtype == x.dtype
+            and (bias is None or bias.dtype == x.dtype)
+            and os.environ.get("CHINESENER_NO_FUSED_DROPOUT") != "1"
+            and not torch.is_autocast_enabled()):
+        H = weight.shape[0]
+        y = _LinearDropoutAddLNFn.apply(
+            x, weight, bias,
+            residual.to(x.dtype).reshape(-1, H).contiguous(),
+            ln_w, ln_b, eps, 1.0 - p)
+        return y.reshape(*x.shape[:-1], H)
+    return dropout_add_layernorm(linear(x, weight, bias), residual, ln_w,
+                                 ln_b, eps, p, training)
 
 
 # ---------------------------------------------------- embedding gather

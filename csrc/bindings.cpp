@@ -27,6 +27,12 @@ std::vector<at::Tensor> dropout_add_ln_fwd(const at::Tensor&,
                                            const at::Tensor&, double, double,
                                            const at::Tensor&);
 at::Tensor mask_scale(const at::Tensor&, const at::Tensor&, double);
+std::vector<at::Tensor> dropout_add_ln_bwd(const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&, double, bool);
 void bump_counter(const at::Tensor&);
 at::Tensor wgrad(const at::Tensor&, const at::Tensor&, long);
 at::Tensor wgrad2(const at::Tensor&, const at::Tensor&, long);
@@ -114,6 +120,7 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("colsum", &colsum);
   m.def("dropout_add_ln_fwd", &dropout_add_ln_fwd);
   m.def("mask_scale", &mask_scale);
+  m.def("dropout_add_ln_bwd", &dropout_add_ln_bwd);
   m.def("bump_counter", &bump_counter);
   m.def("wgrad", &wgrad);
   m.def("wgrad2", &wgrad2);

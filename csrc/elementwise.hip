@@ -168,54 +168,77 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
 }
 
 
-// fast bf16 backward: 32 rows/block (8 per wave), vectorized loads,
-// dw/db accumulated in registers then combined via LDS; H <= 1024.
-// (2 rows/wave was tried: the 4x extra global dw/db atomics cost more
-// than the shorter serial row loop saves.)
-__global__ __launch_bounds__(256) void layernorm_bwd_bf16_kernel(
+// fast bf16 backward, one pass, no global atomics. 16 rows per 4-wave
+// block, 4 per wave, 2 blocks per CU at 8192 rows (holding two rows'
+// loads explicitly, or 2 or 8 rows per wave, measured 2-5 us slower:
+// profiles/fused_bwd_r03.md), vectorized loads.
+// The column reductions (dw = sum dy*xhat, db = sum dy and, with DBIAS,
+// the bias grad of the linear that feeds the dropout) accumulate in
+// registers over a wave's rows, are combined across the block's waves
+// through LDS in wave order, and leave as one fp32 partial row per
+// block in slab[nblocks][K*H]; slab_colsum_kernel sums those per
+// column. Plain stores instead of same-address atomics (guide G12), and
+// the result is bitwise reproducible. H % 8 == 0, H <= 1024.
+// DROPOUT also emits dx_drop = bf16(float(dsum_bf16) * mask * scale),
+// the exact arithmetic of mask_scale_kernel on the stored dsum.
+#define LNB_WAVES 4
+#define LNB_RPW 4
+#define LNB_ROWS (LNB_WAVES * LNB_RPW)
+
+template <bool DROPOUT, bool DBIAS>
+__global__ __launch_bounds__(LNB_WAVES * WAVE) void layernorm_bwd_bf16_kernel(
     const bf16* __restrict__ dy, const bf16* __restrict__ x,
     const float* __restrict__ w, const float* __restrict__ mean,
-    const float* __restrict__ rstd, bf16* __restrict__ dx,
-    float* __restrict__ dw, float* __restrict__ db, long N, int H) {
+    const float* __restrict__ rstd, const unsigned char* __restrict__ mask,
+    bf16* __restrict__ dx, bf16* __restrict__ dx_drop,
+    float* __restrict__ slab, long N, int H, float scale) {
+  static_assert(DROPOUT || !DBIAS, "DBIAS needs DROPOUT");
+  constexpr int K = DBIAS ? 3 : 2;
+  constexpr int MAXC = 2;               // H <= 1024
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* dw_s = reinterpret_cast<float*>(smem_raw);
-  float* db_s = dw_s + H;
-  for (int i = threadIdx.x; i < 2 * H; i += blockDim.x) dw_s[i] = 0.f;
-  __syncthreads();
+  float* part = reinterpret_cast<float*>(smem_raw);  // [LNB_WAVES][K*H]
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
   const int HV = H / 8;                 // vec8 slots per row
-  constexpr int MAXC = 2;               // H <= 1024
-  float dwp[MAXC][8] = {}, dbp[MAXC][8] = {};
+  float dwp[MAXC][8] = {}, dbp[MAXC][8] = {}, dbiasp[MAXC][8] = {};
   float wv[MAXC][8];
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int i = lane + c * WAVE;
     if (i < HV) {
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(w + i * 8);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(w + i * 8 + 4);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) wv[c][e] = w[i * 8 + e];
+      for (int e = 0; e < 8; ++e) wv[c][e] = e < 4 ? lo[e] : hi[e - 4];
     }
   }
-  for (int rr = 0; rr < 8; ++rr) {
-    const long row = (long)blockIdx.x * 32 + wid * 8 + rr;
-    if (row >= N) break;
-    const bf16* dyr = dy + row * H;
-    const bf16* xr = x + row * H;
+  const long row0 = (long)blockIdx.x * LNB_ROWS + wid * LNB_RPW;
+#pragma unroll
+  for (int rr = 0; rr < LNB_RPW; ++rr) {
+    const long row = row0 + rr;
+    if (row >= N) break;                // wave-uniform
     const float m = mean[row], rs = rstd[row];
-    float xh[MAXC][8], dyv[MAXC][8];
+    s16x8 rd[MAXC], rx[MAXC];
+    f32x2 rm[MAXC];                     // 8 mask bytes
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const int i = lane + c * WAVE;
+      if (i < HV) {
+        rd[c] = reinterpret_cast<const s16x8*>(dy + row * H)[i];
+        rx[c] = reinterpret_cast<const s16x8*>(x + row * H)[i];
+        if (DROPOUT) rm[c] = reinterpret_cast<const f32x2*>(mask + row * H)[i];
+      }
+    }
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       const int i = lane + c * WAVE;
       if (i < HV) {
-        const s16x8 rd = reinterpret_cast<const s16x8*>(dyr)[i];
-        const s16x8 rx = reinterpret_cast<const s16x8*>(xr)[i];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float d = to_f32(reinterpret_cast<const bf16*>(&rd)[e]);
-          const float hx = (to_f32(reinterpret_cast<const bf16*>(&rx)[e]) - m) * rs;
-          dyv[c][e] = d;
-          xh[c][e] = hx;
+          const float d = to_f32(reinterpret_cast<const bf16*>(&rd[c])[e]);
+          const float hx =
+              (to_f32(reinterpret_cast<const bf16*>(&rx[c])[e]) - m) * rs;
           const float g = d * wv[c][e];
           c1 += g * hx;
           c2 += g;
@@ -224,39 +247,104 @@ __global__ __launch_bounds__(256) void layernorm_bwd_bf16_kernel(
     }
     c1 = wave_reduce_sum(c1) / H;
     c2 = wave_reduce_sum(c2) / H;
-    bf16* dxr = dx + row * H;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       const int i = lane + c * WAVE;
       if (i < HV) {
-        bf16 outv[8];
+        bf16 outv[8], dropv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float g = dyv[c][e] * wv[c][e];
-          from_f32((g - c2 - xh[c][e] * c1) * rs, &outv[e]);
-          dwp[c][e] += dyv[c][e] * xh[c][e];
-          dbp[c][e] += dyv[c][e];
+          // d, xhat re-derived from the raw bf16 (same values as above)
+          // rather than held in 32 more registers
+          const float d = to_f32(reinterpret_cast<const bf16*>(&rd[c])[e]);
+          const float hx =
+              (to_f32(reinterpret_cast<const bf16*>(&rx[c])[e]) - m) * rs;
+          const float g = d * wv[c][e];
+          from_f32((g - c2 - hx * c1) * rs, &outv[e]);
+          dwp[c][e] += d * hx;
+          dbp[c][e] += d;
+          if (DROPOUT) {
+            const unsigned char mk =
+                reinterpret_cast<const unsigned char*>(&rm[c])[e];
+            dropv[e] = __float2bfloat16(to_f32(outv[e]) * mk * scale);
+            if (DBIAS) dbiasp[c][e] += to_f32(dropv[e]);
+          }
         }
-        reinterpret_cast<s16x8*>(dxr)[i] = *reinterpret_cast<s16x8*>(outv);
+        reinterpret_cast<s16x8*>(dx + row * H)[i] =
+            *reinterpret_cast<s16x8*>(outv);
+        if (DROPOUT)
+          reinterpret_cast<s16x8*>(dx_drop + row * H)[i] =
+              *reinterpret_cast<s16x8*>(dropv);
       }
     }
   }
+  // per-wave partials -> LDS (every wave, also one without a valid row:
+  // its zeros are part of the sum), then a fixed wave-order sum per
+  // column -> this block's slab row, all K*H columns of it
+  float* mine = part + (long)wid * K * H;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int i = lane + c * WAVE;
     if (i < HV) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        atomicAdd(&dw_s[i * 8 + e], dwp[c][e]);
-        atomicAdd(&db_s[i * 8 + e], dbp[c][e]);
+        mine[i * 8 + e] = dwp[c][e];
+        mine[H + i * 8 + e] = dbp[c][e];
+        if (DBIAS) mine[2 * H + i * 8 + e] = dbiasp[c][e];
       }
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < H; i += blockDim.x) {
-    atomicAdd(&dw[i], dw_s[i]);
-    atomicAdd(&db[i], db_s[i]);
+  float* srow = slab + (long)blockIdx.x * K * H;
+  for (int i = threadIdx.x; i < K * H; i += blockDim.x) {
+    float a = part[i];
+#pragma unroll
+    for (int v = 1; v < LNB_WAVES; ++v) a += part[(long)v * K * H + i];
+    srow[i] = a;
   }
+}
+
+// Column sums of an fp32 partial slab [R][C] in a fixed order (rows
+// strided over 8 slices per column, then the slices in order): columns
+// [0, CA) go to outA, the rest to outB, each in its own dtype. Finishes
+// the LN backward and bias_gelu backward reductions.
+#define SCS_COLS 32
+#define SCS_SLICES 8
+template <typename TA, typename TB>
+__global__ __launch_bounds__(SCS_COLS * SCS_SLICES) void slab_colsum_kernel(
+    const float* __restrict__ slab, int R, int C, TA* __restrict__ outA,
+    int CA, TB* __restrict__ outB) {
+  __shared__ float red[SCS_SLICES][SCS_COLS];
+  const int tx = threadIdx.x % SCS_COLS;
+  const int ty = threadIdx.x / SCS_COLS;
+  const int col = blockIdx.x * SCS_COLS + tx;
+  float acc = 0.f;
+  if (col < C) {
+#pragma unroll 8
+    for (int r = ty; r < R; r += SCS_SLICES) acc += slab[(long)r * C + col];
+  }
+  red[ty][tx] = acc;
+  __syncthreads();
+  if (ty == 0 && col < C) {
+    float a = red[0][tx];
+#pragma unroll
+    for (int v = 1; v < SCS_SLICES; ++v) a += red[v][tx];
+    if (col < CA)
+      from_f32(a, &outA[col]);
+    else
+      from_f32(a, &outB[col - CA]);
+  }
+}
+
+template <typename TA, typename TB>
+static void launch_slab_colsum(const at::Tensor& slab, void* outA, int CA,
+                               void* outB, hipStream_t stream) {
+  const int R = slab.size(0);
+  const int C = slab.size(1);
+  hipLaunchKernelGGL((slab_colsum_kernel<TA, TB>),
+                     dim3((C + SCS_COLS - 1) / SCS_COLS),
+                     dim3(SCS_COLS * SCS_SLICES), 0, stream,
+                     slab.data_ptr<float>(), R, C, (TA*)outA, CA, (TB*)outB);
 }
 
 // ---------------------------------------------------------------------
@@ -281,34 +369,81 @@ __device__ __forceinline__ float dgelu_f(float u) {
   return 0.5f * (1.f + t) + 0.5f * u * (1.f - t * t) * da;
 }
 
-template <typename T, bool BWD>
+// 8 consecutive bias values as fp32, from the bias in its stored dtype
+// (a bf16 parameter is read in place, no per-call cast kernel)
+__device__ __forceinline__ void load_bias8(const float* bias, int col0,
+                                           float* be) {
+  const f32x4 lo = *reinterpret_cast<const f32x4*>(bias + col0);
+  const f32x4 hi = *reinterpret_cast<const f32x4*>(bias + col0 + 4);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) be[e] = e < 4 ? lo[e] : hi[e - 4];
+}
+__device__ __forceinline__ void load_bias8(const bf16* bias, int col0,
+                                           float* be) {
+  const s16x8 raw = *reinterpret_cast<const s16x8*>(bias + col0);
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    be[e] = to_f32(reinterpret_cast<const bf16*>(&raw)[e]);
+}
+
+template <typename T, typename BT>
 __global__ void bias_gelu_kernel(const T* __restrict__ x,
-                                 const float* __restrict__ bias,
-                                 const T* __restrict__ dy,  // BWD only
+                                 const BT* __restrict__ bias,
                                  T* __restrict__ out, long n, int F) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long nv = n / 8;
   for (long v = i; v < nv; v += (long)gridDim.x * blockDim.x) {
     const s16x8 raw = reinterpret_cast<const s16x8*>(x)[v];
-    s16x8 draw{};
-    if (BWD) draw = reinterpret_cast<const s16x8*>(dy)[v];
     const int col0 = (int)((v * 8) % F);
-    const f32x4 b_lo = *reinterpret_cast<const f32x4*>(bias + col0);
-    const f32x4 b_hi = *reinterpret_cast<const f32x4*>(bias + col0 + 4);
+    float be[8];
+    load_bias8(bias, col0, be);
     T o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float be = e < 4 ? b_lo[e] : b_hi[e - 4];
-      const float u = to_f32(reinterpret_cast<const T*>(&raw)[e]) + be;
-      if (BWD) {
-        const float g = to_f32(reinterpret_cast<const T*>(&draw)[e]);
-        from_f32(g * dgelu_f(u), &o[e]);
-      } else {
-        from_f32(gelu_f(u), &o[e]);
-      }
+      const float u = to_f32(reinterpret_cast<const T*>(&raw)[e]) + be[e];
+      from_f32(gelu_f(u), &o[e]);
     }
     reinterpret_cast<s16x8*>(out)[v] = *reinterpret_cast<s16x8*>(o);
   }
+}
+
+// backward with the bias grad fused: grid (column chunk, row chunk);
+// a thread owns one vec8 column slot, walks the rows of its chunk and
+// accumulates sum float(dx_bf16) in registers; the block's partial row
+// goes to slab[row chunk][F] for slab_colsum_kernel. Every block writes
+// all the columns of its chunk, so the slab needs no zero-fill.
+#define BGB_THREADS 64
+#define BGB_ROWS 16
+template <typename T, typename BT>
+__global__ __launch_bounds__(BGB_THREADS) void bias_gelu_bwd_kernel(
+    const T* __restrict__ x, const BT* __restrict__ bias,
+    const T* __restrict__ dy, T* __restrict__ dx, float* __restrict__ slab,
+    long M, int F) {
+  const int slot = blockIdx.x * BGB_THREADS + threadIdx.x;
+  if (slot >= F / 8) return;
+  const int col0 = slot * 8;
+  float be[8], acc[8] = {};
+  load_bias8(bias, col0, be);
+  const long r0 = (long)blockIdx.y * BGB_ROWS;
+  const long r1 = min(M, r0 + BGB_ROWS);
+#pragma unroll 4
+  for (long r = r0; r < r1; ++r) {
+    const long off = r * F + col0;
+    const s16x8 raw = *reinterpret_cast<const s16x8*>(x + off);
+    const s16x8 draw = *reinterpret_cast<const s16x8*>(dy + off);
+    T o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float u = to_f32(reinterpret_cast<const T*>(&raw)[e]) + be[e];
+      const float g = to_f32(reinterpret_cast<const T*>(&draw)[e]);
+      from_f32(g * dgelu_f(u), &o[e]);
+      acc[e] += to_f32(o[e]);
+    }
+    *reinterpret_cast<s16x8*>(dx + off) = *reinterpret_cast<s16x8*>(o);
+  }
+  float* srow = slab + (long)blockIdx.y * F + col0;
+  *reinterpret_cast<f32x4*>(srow) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+  *reinterpret_cast<f32x4*>(srow + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
 }
 
 __global__ void bias_gelu_kernel_f32(const float* __restrict__ x,
@@ -436,11 +571,99 @@ std::vector<at::Tensor> add_layernorm_fwd(const at::Tensor& x,
   return layernorm_fwd_impl(x, res, w, b, eps, true);
 }
 
+// bf16 LN backward on the one-pass kernel. mask undefined: plain LN
+// backward -> {dx, dw, db}; mask defined: the dropout+add+LN backward ->
+// {dsum, dx_drop, dw, db, dbias-or-undefined}. dw/db come out in w's
+// dtype, dbias in the activation dtype, straight from the finisher.
+static std::vector<at::Tensor> layernorm_bwd_bf16(
+    const at::Tensor& dy, const at::Tensor& x, const at::Tensor& w,
+    const at::Tensor& mean, const at::Tensor& rstd, const at::Tensor& mask,
+    double keep, bool want_dbias) {
+  const long N = x.size(0);
+  const int H = x.size(1);
+  TORCH_CHECK(H % 8 == 0 && H <= 1024, "layernorm bwd bf16: bad H ", H);
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.numel() == x.numel(),
+              "layernorm bwd bf16: dy must be bf16 of x's shape");
+  TORCH_CHECK(mean.is_cuda() && mean.is_contiguous() &&
+                  mean.scalar_type() == at::kFloat && mean.numel() == N &&
+                  rstd.is_cuda() && rstd.is_contiguous() &&
+                  rstd.scalar_type() == at::kFloat && rstd.numel() == N,
+              "layernorm bwd bf16: mean/rstd must be fp32 [N]");
+  TORCH_CHECK(w.is_cuda() && w.numel() == H, "layernorm bwd bf16: bad weight");
+  const bool dropout = mask.defined();
+  if (dropout) {
+    TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() &&
+                    mask.scalar_type() == at::kByte &&
+                    mask.numel() == x.numel(),
+                "dropout_add_ln_bwd: mask must be uint8 of x's shape");
+  }
+  const int K = (dropout && want_dbias) ? 3 : 2;
+  const long nblocks = std::max<long>((N + LNB_ROWS - 1) / LNB_ROWS, 1);
+  auto dx = at::empty_like(x);
+  auto dx_drop = dropout ? at::empty_like(x) : at::Tensor();
+  auto wf = w.to(at::kFloat).contiguous();
+  auto slab = at::empty({nblocks, (long)K * H}, x.options().dtype(at::kFloat));
+  const bool w_bf16 = w.scalar_type() == at::kBFloat16;
+  // other weight dtypes: finish in fp32 and cast
+  auto dwdb = at::empty(
+      {2, (long)H}, x.options().dtype(w_bf16 ? at::kBFloat16 : at::kFloat));
+  auto dbias = K == 3 ? at::empty({(long)H}, x.options()) : at::Tensor();
+  const size_t smem = (size_t)LNB_WAVES * K * H * sizeof(float);
+  const float scale = (float)(1.0 / keep);
+  auto stream = cur_stream(x);
+#define LNB_LAUNCH(DROPOUT, DBIAS)                                           \
+  hipLaunchKernelGGL((layernorm_bwd_bf16_kernel<DROPOUT, DBIAS>),            \
+                     dim3((unsigned)nblocks), dim3(LNB_WAVES * WAVE), smem,  \
+                     stream, (const bf16*)dy.data_ptr(),                     \
+                     (const bf16*)x.data_ptr(), wf.data_ptr<float>(),        \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),         \
+                     dropout ? mask.data_ptr<unsigned char>() : nullptr,     \
+                     (bf16*)dx.data_ptr(),                                   \
+                     dropout ? (bf16*)dx_drop.data_ptr() : nullptr,          \
+                     slab.data_ptr<float>(), N, H, scale)
+  if (K == 3) {
+    LNB_LAUNCH(true, true);
+  } else if (dropout) {
+    LNB_LAUNCH(true, false);
+  } else {
+    LNB_LAUNCH(false, false);
+  }
+#undef LNB_LAUNCH
+  void* ob = K == 3 ? dbias.data_ptr() : nullptr;
+  if (w_bf16)
+    launch_slab_colsum<bf16, bf16>(slab, dwdb.data_ptr(), 2 * H, ob, stream);
+  else
+    launch_slab_colsum<float, bf16>(slab, dwdb.data_ptr(), 2 * H, ob, stream);
+  HIP_CHECK_LAST();
+  auto dw = dwdb[0], db = dwdb[1];
+  if (dw.scalar_type() != w.scalar_type()) {
+    dw = dw.to(w.scalar_type());
+    db = db.to(w.scalar_type());
+  }
+  if (dropout) return {dx, dx_drop, dw, db, dbias};
+  return {dx, dw, db};
+}
+
+std::vector<at::Tensor> dropout_add_ln_bwd(
+    const at::Tensor& dy, const at::Tensor& s, const at::Tensor& w,
+    const at::Tensor& mean, const at::Tensor& rstd, const at::Tensor& mask,
+    double keep, bool want_dbias) {
+  CHECK_CUDA_CONTIG(dy);
+  CHECK_CUDA_CONTIG(s);
+  TORCH_CHECK(s.scalar_type() == at::kBFloat16 && s.dim() == 2,
+              "dropout_add_ln_bwd: bf16 [N, H] only");
+  TORCH_CHECK(mask.defined() && keep > 0.0,
+              "dropout_add_ln_bwd: needs the saved mask and keep > 0");
+  return layernorm_bwd_bf16(dy, s, w, mean, rstd, mask, keep, want_dbias);
+}
+
 std::vector<at::Tensor> layernorm_bwd(const at::Tensor& dy, const at::Tensor& x,
                                       const at::Tensor& w, const at::Tensor& mean,
                                       const at::Tensor& rstd) {
   CHECK_CUDA_CONTIG(dy);
   CHECK_CUDA_CONTIG(x);
+  if (x.scalar_type() == at::kBFloat16)
+    return layernorm_bwd_bf16(dy, x, w, mean, rstd, at::Tensor(), 1.0, false);
   const long N = x.size(0);
   const int H = x.size(1);
   auto dx = at::empty_like(x);
@@ -449,15 +672,7 @@ std::vector<at::Tensor> layernorm_bwd(const at::Tensor& dy, const at::Tensor& x,
   auto wf = w.to(at::kFloat).contiguous();
   const size_t smem = 2 * H * sizeof(float);
   auto stream = cur_stream(x);
-  if (x.scalar_type() == at::kBFloat16) {
-    TORCH_CHECK(H % 8 == 0 && H <= 1024, "layernorm bwd bf16: bad H ", H);
-    hipLaunchKernelGGL(layernorm_bwd_bf16_kernel, dim3((N + 31) / 32),
-                       dim3(256), smem, stream,
-                       (const bf16*)dy.data_ptr(), (const bf16*)x.data_ptr(),
-                       wf.data_ptr<float>(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), (bf16*)dx.data_ptr(),
-                       dw.data_ptr<float>(), db.data_ptr<float>(), N, H);
-  } else {
+  {
     const int rows_per_blk = 4;
     const dim3 grid((N + rows_per_blk - 1) / rows_per_blk);
     const dim3 block(rows_per_blk * WAVE);
@@ -471,48 +686,96 @@ std::vector<at::Tensor> layernorm_bwd(const at::Tensor& dy, const at::Tensor& x,
   return {dx, dw.to(w.scalar_type()), db.to(w.scalar_type())};
 }
 
-static at::Tensor bias_gelu_impl(const at::Tensor& x, const at::Tensor& bias,
-                                 const c10::optional<at::Tensor>& dy) {
+// bias in its stored dtype when the kernels can read it in place (bf16
+// or fp32, contiguous), else an fp32 copy
+static at::Tensor bias_gelu_bias(const at::Tensor& bias, int F) {
+  TORCH_CHECK(bias.is_cuda() && bias.numel() == F, "bias_gelu: bad bias");
+  if (bias.is_contiguous() && (bias.scalar_type() == at::kBFloat16 ||
+                               bias.scalar_type() == at::kFloat))
+    return bias;
+  return bias.to(at::kFloat).contiguous();
+}
+
+at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
   CHECK_CUDA_CONTIG(x);
   const long n = x.numel();
   const int F = x.size(-1);
   TORCH_CHECK(F % 8 == 0, "bias_gelu: F % 8 != 0");
   auto out = at::empty_like(x);
-  auto bf = bias.to(at::kFloat).contiguous();
   auto stream = cur_stream(x);
   const int block = 256;
   if (x.scalar_type() == at::kBFloat16) {
+    auto b = bias_gelu_bias(bias, F);
     const long grid = std::min<long>((n / 8 + block - 1) / block, 32768);
-    if (dy) {
-      hipLaunchKernelGGL((bias_gelu_kernel<bf16, true>), dim3(grid), dim3(block),
-                         0, stream, (const bf16*)x.data_ptr(),
-                         bf.data_ptr<float>(), (const bf16*)dy->data_ptr(),
-                         (bf16*)out.data_ptr(), n, F);
-    } else {
-      hipLaunchKernelGGL((bias_gelu_kernel<bf16, false>), dim3(grid), dim3(block),
-                         0, stream, (const bf16*)x.data_ptr(),
-                         bf.data_ptr<float>(), nullptr,
-                         (bf16*)out.data_ptr(), n, F);
-    }
+    if (b.scalar_type() == at::kBFloat16)
+      hipLaunchKernelGGL((bias_gelu_kernel<bf16, bf16>), dim3(grid),
+                         dim3(block), 0, stream, (const bf16*)x.data_ptr(),
+                         (const bf16*)b.data_ptr(), (bf16*)out.data_ptr(), n,
+                         F);
+    else
+      hipLaunchKernelGGL((bias_gelu_kernel<bf16, float>), dim3(grid),
+                         dim3(block), 0, stream, (const bf16*)x.data_ptr(),
+                         b.data_ptr<float>(), (bf16*)out.data_ptr(), n, F);
   } else {
+    auto bf = bias.to(at::kFloat).contiguous();
     const long grid = std::min<long>((n + block - 1) / block, 4096);
     hipLaunchKernelGGL(bias_gelu_kernel_f32, dim3(grid), dim3(block), 0, stream,
-                       x.data_ptr<float>(), bf.data_ptr<float>(),
-                       dy ? dy->data_ptr<float>() : nullptr, (bool)dy,
-                       out.data_ptr<float>(), n, F);
+                       x.data_ptr<float>(), bf.data_ptr<float>(), nullptr,
+                       false, out.data_ptr<float>(), n, F);
   }
   HIP_CHECK_LAST();
   return out;
 }
 
-at::Tensor bias_gelu_fwd(const at::Tensor& x, const at::Tensor& bias) {
-  return bias_gelu_impl(x, bias, c10::nullopt);
-}
-
 std::vector<at::Tensor> bias_gelu_bwd(const at::Tensor& dy, const at::Tensor& x,
                                       const at::Tensor& bias) {
-  auto dx = bias_gelu_impl(x, bias, dy);
-  auto dbias = at::sum(dx, {0}, false, at::kFloat).to(bias.scalar_type());
+  CHECK_CUDA_CONTIG(x);
+  CHECK_CUDA_CONTIG(dy);
+  const long n = x.numel();
+  const int F = x.size(-1);
+  TORCH_CHECK(F % 8 == 0, "bias_gelu: F % 8 != 0");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.numel() == n,
+              "bias_gelu_bwd: dy must match x");
+  auto dx = at::empty_like(x);
+  auto stream = cur_stream(x);
+  if (x.scalar_type() != at::kBFloat16) {
+    auto bf = bias.to(at::kFloat).contiguous();
+    const int block = 256;
+    const long grid = std::min<long>((n + block - 1) / block, 4096);
+    hipLaunchKernelGGL(bias_gelu_kernel_f32, dim3(grid), dim3(block), 0, stream,
+                       x.data_ptr<float>(), bf.data_ptr<float>(),
+                       dy.data_ptr<float>(), true, dx.data_ptr<float>(), n, F);
+    HIP_CHECK_LAST();
+    auto dbias = at::sum(dx.reshape({-1, (long)F}), {0}, false, at::kFloat)
+                     .to(bias.scalar_type());
+    return {dx, dbias};
+  }
+  auto b = bias_gelu_bias(bias, F);
+  const long M = n / F;
+  const long nchunks = std::max<long>((M + BGB_ROWS - 1) / BGB_ROWS, 1);
+  TORCH_CHECK(nchunks <= 65535, "bias_gelu_bwd: too many rows ", M);
+  auto slab = at::empty({nchunks, (long)F}, x.options().dtype(at::kFloat));
+  const bool b_bf16 = b.scalar_type() == at::kBFloat16;
+  auto dbias = at::empty({(long)F},
+                         x.options().dtype(b_bf16 ? at::kBFloat16 : at::kFloat));
+  const dim3 grid((F / 8 + BGB_THREADS - 1) / BGB_THREADS, (unsigned)nchunks);
+  if (b_bf16) {
+    hipLaunchKernelGGL((bias_gelu_bwd_kernel<bf16, bf16>), grid,
+                       dim3(BGB_THREADS), 0, stream, (const bf16*)x.data_ptr(),
+                       (const bf16*)b.data_ptr(), (const bf16*)dy.data_ptr(),
+                       (bf16*)dx.data_ptr(), slab.data_ptr<float>(), M, F);
+    launch_slab_colsum<bf16, bf16>(slab, dbias.data_ptr(), F, nullptr, stream);
+  } else {
+    hipLaunchKernelGGL((bias_gelu_bwd_kernel<bf16, float>), grid,
+                       dim3(BGB_THREADS), 0, stream, (const bf16*)x.data_ptr(),
+                       b.data_ptr<float>(), (const bf16*)dy.data_ptr(),
+                       (bf16*)dx.data_ptr(), slab.data_ptr<float>(), M, F);
+    launch_slab_colsum<float, float>(slab, dbias.data_ptr(), F, nullptr,
+                                     stream);
+  }
+  HIP_CHECK_LAST();
+  if (dbias.scalar_type() != bias.scalar_type())
+    dbias = dbias.to(bias.scalar_type());
   return {dx, dbias};
 }
 

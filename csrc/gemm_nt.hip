@@ -67,11 +67,13 @@ __device__ __forceinline__ bfrag frag(const bf16* tile, int r0, int k0) {
       tile + ((long)row << 6) + (swz_chunk(row, chunk) << 3));
 }
 
-template <typename OT, bool HAS_BIAS>
+// BT: the bias in its stored dtype (fp32 or bf16, read in place and
+// added in fp32); ignored without HAS_BIAS
+template <typename OT, bool HAS_BIAS, typename BT>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(
     const bf16* __restrict__ A,   // [M, K]
     const bf16* __restrict__ B,   // [N, K]
-    const float* __restrict__ bias,  // [N] fp32 or null
+    const BT* __restrict__ bias,  // [N] or null
     OT* __restrict__ C,           // [M, N]
     long M, long N, long K, int tiles_n) {
   __shared__ bf16 smem[2 * 2 * BM * BK];     // A/B double-buffered, 64 KiB
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long col = n0 + wc + j * 16 + (lane & 15);
-      const float bv = HAS_BIAS ? bias[col] : 0.f;
+      const float bv = HAS_BIAS ? to_f32(bias[col]) : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         from_f32(acc[i][j][r] + bv, &C[(row0 + r) * N + col]);
@@ -153,21 +155,25 @@ static void launch_gemm_nt(const at::Tensor& a, const at::Tensor& b,
                            const c10::optional<at::Tensor>& bias,
                            at::Tensor& out, long M, long N, long K) {
   dim3 grid((unsigned)((M / BM) * (N / BN)));
-  const float* bp =
-      bias ? bias->data_ptr<float>() : nullptr;
-  if (bp)
-    hipLaunchKernelGGL((gemm_nt_kernel<OT, true>), grid, dim3(256), 0,
+  if (bias && bias->scalar_type() == at::kBFloat16)
+    hipLaunchKernelGGL((gemm_nt_kernel<OT, true, bf16>), grid, dim3(256), 0,
                        cur_stream(a), (const bf16*)a.data_ptr(),
-                       (const bf16*)b.data_ptr(), bp, (OT*)out.data_ptr(),
+                       (const bf16*)b.data_ptr(),
+                       (const bf16*)bias->data_ptr(), (OT*)out.data_ptr(),
                        M, N, K, (int)(N / BN));
-  else
-    hipLaunchKernelGGL((gemm_nt_kernel<OT, false>), grid, dim3(256), 0,
+  else if (bias)
+    hipLaunchKernelGGL((gemm_nt_kernel<OT, true, float>), grid, dim3(256), 0,
                        cur_stream(a), (const bf16*)a.data_ptr(),
-                       (const bf16*)b.data_ptr(), nullptr,
+                       (const bf16*)b.data_ptr(), bias->data_ptr<float>(),
+                       (OT*)out.data_ptr(), M, N, K, (int)(N / BN));
+  else
+    hipLaunchKernelGGL((gemm_nt_kernel<OT, false, float>), grid, dim3(256), 0,
+                       cur_stream(a), (const bf16*)a.data_ptr(),
+                       (const bf16*)b.data_ptr(), (const float*)nullptr,
                        (OT*)out.data_ptr(), M, N, K, (int)(N / BN));
 }
 
-// C = A @ B^T (+bias). A [M,K] bf16, B [N,K] bf16, bias fp32 optional;
+// C = A @ B^T (+bias). A [M,K] bf16, B [N,K] bf16, bias fp32/bf16 optional;
 // out bf16 (fp32_out=false) or fp32.
 at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b,
                    c10::optional<at::Tensor> bias, bool fp32_out) {
@@ -183,9 +189,10 @@ at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b,
               "x", K, ")");
   if (bias) {
     TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
-                    bias->scalar_type() == at::kFloat &&
+                    (bias->scalar_type() == at::kFloat ||
+                     bias->scalar_type() == at::kBFloat16) &&
                     bias->numel() == N,
-                "gemm_nt: bias must be fp32 [N]");
+                "gemm_nt: bias must be fp32 or bf16 [N]");
   }
   auto out = at::empty({M, N}, a.options().dtype(
                                    fp32_out ? at::kFloat : at::kBFloat16));
