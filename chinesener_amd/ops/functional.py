@@ -436,35 +436,63 @@ def bias_gelu(x, bias):
 
 
 # ------------------------------------------------------------ attention
+def _attn_path(L: int, D: int, dtype, on_gpu: bool) -> str:
+    """Which attention implementation serves a [.., L, D] problem:
+    'lds'   full-LDS kernel (csrc/attention.hip), padded L <= 176 i.e.
+            L <= 160;
+    'tiled' K/V-tiled online-softmax kernel (csrc/attention_tiled.hip),
+            L <= 512;
+    'torch' the unfused reference path (fp32, CPU, D > 64, L > 512).
+    CHINESENER_ATTN_TILED (read at call time): 'off' restores the torch
+    fallback above 160, 'force' sends every L <= 512 to the tiled
+    kernels; unset gives the default above."""
+    if not on_gpu or dtype != torch.bfloat16 or D > 64 or L < 1:
+        return "torch"
+    mode = os.environ.get("CHINESENER_ATTN_TILED", "")
+    if mode == "force":
+        return "tiled" if L <= 512 else "torch"
+    if ((L + 31) // 32) * 32 <= 176:
+        return "lds"
+    if mode != "off" and L <= 512:
+        return "tiled"
+    return "torch"
+
+
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, lens, scale):
-        out, lse = get_ext().attn_fwd(q, k, v, lens, scale, 1.0, None)
+    def forward(ctx, q, k, v, lens, scale, tiled=False):
+        ext = get_ext()
+        fwd = ext.attn_tiled_fwd if tiled else ext.attn_fwd
+        out, lse = fwd(q, k, v, lens, scale, 1.0, None)
         ctx.save_for_backward(q, k, v, out, lse, lens)
         ctx.scale = scale
+        ctx.tiled = tiled
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse, lens = ctx.saved_tensors
-        dq, dk, dv = get_ext().attn_bwd(dout.contiguous(), q, k, v, out, lse,
-                                        lens, ctx.scale, 1.0, None)
-        return dq, dk, dv, None, None
+        ext = get_ext()
+        bwd = ext.attn_tiled_bwd if ctx.tiled else ext.attn_bwd
+        dq, dk, dv = bwd(dout.contiguous(), q, k, v, out, lse, lens,
+                         ctx.scale, 1.0, None)
+        return dq, dk, dv, None, None, None
 
 
 def attention(q, k, v, mask: Optional[torch.Tensor] = None,
               scale: Optional[float] = None, lens: Optional[torch.Tensor] = None):
     """Fused attention. q,k,v [B,H,L,D]; mask [B,L] prefix mask or lens [B].
 
-    HIP path: bf16, head dim padded to 32/64, padded L <= 176 i.e.
-    L <= 160 (the kernel pads L to a multiple of 32; covers every
-    reference NER config — L=150). Longer sequences (MRC's ragged
-    batches can pad past 160) fall back to the torch path."""
+    HIP path: bf16, head dim padded to 32/64. L <= 160 runs the full-LDS
+    kernel (it pads L to a multiple of 32, padded L <= 176; covers every
+    reference NER config — L=150); 161 <= L <= 512 (MRC's L=170, BERT up
+    to max_position_embeddings) runs the K/V-tiled online-softmax kernel.
+    Only L > 512, fp32 or D > 64 take the torch path; see _attn_path."""
     D = q.shape[-1]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    if (hip_enabled(q) and q.dtype == torch.bfloat16 and D <= 64
-            and ((q.shape[2] + 31) // 32) * 32 <= 176):
+    path = _attn_path(q.shape[2], D, q.dtype, hip_enabled(q))
+    if path != "torch":
         Dp = 32 if D <= 32 else 64
         if lens is None:
             lens = (mask.long().sum(1) if mask is not None
@@ -473,7 +501,8 @@ def attention(q, k, v, mask: Optional[torch.Tensor] = None,
         out = _AttentionFn.apply(_pad_last(q, Dp).contiguous(),
                                  _pad_last(k, Dp).contiguous(),
                                  _pad_last(v, Dp).contiguous(),
-                                 lens.to(torch.int32), float(scale))
+                                 lens.to(torch.int32), float(scale),
+                                 path == "tiled")
         return out[..., :D] if Dp != D else out
     return ref.attention(q, k, v, mask, scale)
 
@@ -485,27 +514,31 @@ class _AttentionQkvFn(torch.autograd.Function):
     backward from the saved seed snapshot (flash-attn style)."""
 
     @staticmethod
-    def forward(ctx, qkv, lens, scale, keep):
+    def forward(ctx, qkv, lens, scale, keep, tiled=False):
         seed = None
         if keep < 1.0:
             ctr = _rng_counter_for(qkv.device)
             seed = ctr.clone()
             get_ext().bump_counter(ctr)
-        out, lse = get_ext().attn_fwd_qkv(qkv, lens, scale, keep, seed)
+        ext = get_ext()
+        fwd = ext.attn_tiled_fwd_qkv if tiled else ext.attn_fwd_qkv
+        out, lse = fwd(qkv, lens, scale, keep, seed)
         ctx.save_for_backward(qkv, out, lse, lens,
                               seed if seed is not None
                               else torch.zeros(0))
         ctx.scale = scale
         ctx.keep = keep
+        ctx.tiled = tiled
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, lens, seed = ctx.saved_tensors
-        (dqkv,) = get_ext().attn_bwd_qkv(dout.contiguous(), qkv, out, lse,
-                                         lens, ctx.scale, ctx.keep,
-                                         seed if seed.numel() else None)
-        return dqkv, None, None, None
+        ext = get_ext()
+        bwd = ext.attn_tiled_bwd_qkv if ctx.tiled else ext.attn_bwd_qkv
+        (dqkv,) = bwd(dout.contiguous(), qkv, out, lse, lens, ctx.scale,
+                      ctx.keep, seed if seed.numel() else None)
+        return dqkv, None, None, None, None
 
 
 def attention_qkv(qkv, mask: Optional[torch.Tensor] = None,
@@ -516,21 +549,26 @@ def attention_qkv(qkv, mask: Optional[torch.Tensor] = None,
 
     qkv: [B, L, 3, H, D] (the natural reshape of the fused QKV GEMM) ->
     [B, L, H, D]. HIP path avoids every layout copy; fallback unpacks.
-    p_drop applies BERT's attention-prob dropout inside the kernel."""
+    L <= 160 runs the full-LDS kernel and 161 <= L <= 512 the K/V-tiled
+    one (see _attn_path); on both, p_drop applies BERT's attention-prob
+    dropout inside the kernel from the shared device counter, so a given
+    (seed, B, H, L) drops the same cells whichever kernel runs."""
     B, L, _, H, D = qkv.shape
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     keep = 1.0 - p_drop if (training and p_drop > 0) else 1.0
     if os.environ.get("CHINESENER_NO_ATTN_DROP") == "1":
         keep = 1.0
-    if (hip_enabled(qkv) and qkv.dtype == torch.bfloat16
-            and D in (32, 64) and ((L + 31) // 32) * 32 <= 176):
+    path = (_attn_path(L, D, qkv.dtype, hip_enabled(qkv))
+            if D in (32, 64) else "torch")
+    if path != "torch":
         if lens is None:
             lens = (mask.long().sum(1) if mask is not None
                     else torch.full((B,), L, dtype=torch.long,
                                     device=qkv.device))
         return _AttentionQkvFn.apply(qkv.contiguous(), lens.to(torch.int32),
-                                     float(scale), float(keep))
+                                     float(scale), float(keep),
+                                     path == "tiled")
     q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # [B,H,L,D]
     if keep < 1.0:
         out = ref.attention(q, k, v, mask, scale, p_drop=p_drop,

@@ -58,10 +58,123 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if mask is not None:
         key_mask = mask[:, None, None, :].to(scores.dtype)
         scores = scores + (1.0 - key_mask) * NEG_INF
-    probs = torch.softmax(scores.float(), dim=-1).to(q.dtype)
+    # softmax in at least fp32; fp64 inputs stay fp64 (the fp64 oracle of
+    # the tiled-attention tests)
+    acc = scores if scores.dtype == torch.float64 else scores.float()
+    probs = torch.softmax(acc, dim=-1).to(q.dtype)
     if training and p_drop > 0:
         probs = F.dropout(probs, p_drop, training)
     return torch.matmul(probs, v)
+
+
+def attention_tiled(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                    lens: torch.Tensor, scale: float, tile_q: int,
+                    tile_k: int, keep: float = 1.0,
+                    keep_mask: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CPU model of csrc/attention_tiled.hip forward: the tile-by-tile
+    online-softmax recurrence, in the dtype of q. q,k,v [B,H,L,D]; lens
+    [B] (>= 1); keep_mask bool [B,H,L,L] (True = kept) when keep < 1.
+
+    Per (batch, query block): running row max m, running row sum l and an
+    O accumulator over the key tiles below lens[b]; key tiles wholly at
+    or beyond lens[b] are skipped; masked keys inside a tile contribute
+    exactly 0. Dropout multiplies the un-normalised tile probabilities
+    that feed P.V, l sums the undropped ones, and 1/(l*keep) is applied
+    once at the end. Returns (out [B,H,L,D], lse [B,H,L])."""
+    B, H, L, D = q.shape
+    out = torch.zeros_like(q)
+    lse = q.new_zeros(B, H, L)
+    for b in range(B):
+        kend = min(int(lens[b]), L)
+        for q0 in range(0, L, tile_q):
+            q1 = min(q0 + tile_q, L)
+            qt = q[b, :, q0:q1]                              # [H,tq,D]
+            m = q.new_full((H, q1 - q0), NEG_INF)
+            l = q.new_zeros(H, q1 - q0)
+            o = q.new_zeros(H, q1 - q0, D)
+            for k0 in range(0, kend, tile_k):
+                k1 = min(k0 + tile_k, L)
+                s = torch.matmul(qt, k[b, :, k0:k1].transpose(-1, -2)) * scale
+                valid = torch.arange(k0, k1, device=q.device) < kend
+                s = torch.where(valid, s, torch.full_like(s, NEG_INF))
+                m_new = torch.maximum(m, s.max(-1).values)
+                alpha = torch.exp(m - m_new)
+                p = torch.where(valid, torch.exp(s - m_new[..., None]),
+                                torch.zeros_like(s))
+                l = l * alpha + p.sum(-1)
+                if keep < 1.0:
+                    p = p * keep_mask[b, :, q0:q1, k0:k1].to(p.dtype)
+                o = o * alpha[..., None] + torch.matmul(p, v[b, :, k0:k1])
+                m = m_new
+            out[b, :, q0:q1] = o / (l * keep)[..., None]
+            lse[b, :, q0:q1] = m + torch.log(l)
+    return out, lse
+
+
+def attention_tiled_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
+                        v: torch.Tensor, out: torch.Tensor, lse: torch.Tensor,
+                        lens: torch.Tensor, scale: float, tile_q: int,
+                        tile_k: int, keep: float = 1.0,
+                        keep_mask: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CPU model of csrc/attention_tiled.hip backward: two sweeps that
+    each recompute P = exp(S*scale - lse) and dP = dO V^T per tile.
+
+    Sweep 1 (per key block, looping over query tiles) accumulates
+    dV += P'^T dO and dK += dS^T Q; key blocks wholly at or beyond
+    lens[b] are written as zeros. Sweep 2 (per query block, looping over
+    key tiles below lens[b]) accumulates dQ += dS K. With the dropout
+    mask M: P' = P*M/keep, dS = P*(dP*M/keep - delta)*scale, and
+    delta = rowsum(dO*O) per query tile. Returns (dq, dk, dv)."""
+    B, H, L, D = q.shape
+    dq = torch.zeros_like(q)
+    dk = torch.zeros_like(k)
+    dv = torch.zeros_like(v)
+
+    def tile(b, q0, q1, k0, k1, kend):
+        s = torch.matmul(q[b, :, q0:q1],
+                         k[b, :, k0:k1].transpose(-1, -2)) * scale
+        valid = torch.arange(k0, k1, device=q.device) < kend
+        p = torch.where(valid, torch.exp(s - lse[b, :, q0:q1, None]),
+                        torch.zeros_like(s))
+        dp = torch.matmul(dout[b, :, q0:q1], v[b, :, k0:k1].transpose(-1, -2))
+        pd = p
+        if keep < 1.0:
+            mk = keep_mask[b, :, q0:q1, k0:k1].to(p.dtype) / keep
+            pd = p * mk
+            dp = dp * mk
+        delta = (dout[b, :, q0:q1] * out[b, :, q0:q1]).sum(-1, keepdim=True)
+        return pd, p * (dp - delta) * scale
+
+    for b in range(B):
+        kend = min(int(lens[b]), L)
+        # sweep 1: dK/dV per key block
+        for k0 in range(0, L, tile_k):
+            k1 = min(k0 + tile_k, L)
+            if k0 >= kend:
+                continue                      # rows stay exactly zero
+            dk_acc = q.new_zeros(H, k1 - k0, D)
+            dv_acc = q.new_zeros(H, k1 - k0, D)
+            for q0 in range(0, L, tile_q):
+                q1 = min(q0 + tile_q, L)
+                pd, ds = tile(b, q0, q1, k0, k1, kend)
+                dv_acc = dv_acc + torch.matmul(pd.transpose(-1, -2),
+                                               dout[b, :, q0:q1])
+                dk_acc = dk_acc + torch.matmul(ds.transpose(-1, -2),
+                                               q[b, :, q0:q1])
+            dk[b, :, k0:k1] = dk_acc
+            dv[b, :, k0:k1] = dv_acc
+        # sweep 2: dQ per query block
+        for q0 in range(0, L, tile_q):
+            q1 = min(q0 + tile_q, L)
+            dq_acc = q.new_zeros(H, q1 - q0, D)
+            for k0 in range(0, kend, tile_k):
+                k1 = min(k0 + tile_k, L)
+                _, ds = tile(b, q0, q1, k0, k1, kend)
+                dq_acc = dq_acc + torch.matmul(ds, k[b, :, k0:k1])
+            dq[b, :, q0:q1] = dq_acc
+    return dq, dk, dv
 
 
 def tener_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

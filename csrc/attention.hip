@@ -15,80 +15,10 @@
 // path consumes the fused-QKV projection output [B,L,3,H,D] directly and
 // writes O as [B,L,H,D] -- zero transpose/copy around the kernel
 // (torch-side reshape of the GEMM output is free).
-#include "common.h"
+#include "attn_common.h"
 
 #define MAXNF 11  // N-tiles of 16: L_pad <= 176
 #define LPAD_MAX 176
-
-using bfrag = mfma_bf16x8;
-using cfrag = mfma_f32x4;
-
-__device__ __forceinline__ bfrag lds_frag(const bf16* base, int i0, int ld,
-                                          int k0) {
-  const int l = threadIdx.x & (WAVE - 1);
-  return *reinterpret_cast<const bfrag*>(base + (long)(i0 + (l & 15)) * ld +
-                                         k0 + ((l >> 4) << 3));
-}
-
-// B operand from a ROW-major [K][N] LDS buffer (per-element reads)
-__device__ __forceinline__ bfrag lds_fragB_rowmajor(const bf16* base, int k0,
-                                                    int ld, int n0) {
-  const int l = threadIdx.x & (WAVE - 1);
-  bfrag b;
-#pragma unroll
-  for (int e = 0; e < 8; ++e)
-    reinterpret_cast<bf16*>(&b)[e] =
-        base[(long)(k0 + ((l >> 4) << 3) + e) * ld + n0 + (l & 15)];
-  return b;
-}
-
-__device__ __forceinline__ cfrag mfma16(bfrag a, bfrag b, cfrag c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// counter-based dropout RNG (same construction as elementwise.hip):
-// splitmix64 hash of (seed, element) -> uniform [0,1)
-__device__ __forceinline__ float attn_hash_uniform(unsigned long long ctr,
-                                                   unsigned long long idx) {
-  unsigned long long z = ctr * 0x9E3779B97F4A7C15ull ^ idx;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (float)(z >> 40) * (1.f / 16777216.f);
-}
-
-// stage a [rows x D] global tile (row stride rs) into LDS [rpad x ld]
-// (ld > D pads the row stride so MFMA operand reads are bank-conflict
-// free: ld*2B/4B/4 odd <=> ld % 16 == 8 for the strides used here)
-__device__ __forceinline__ void stage_tile(const bf16* g, long rs, bf16* s,
-                                           int rows, int rpad, int D,
-                                           int ld) {
-  const int nv = rpad * D / 8;
-  for (int i = threadIdx.x; i < nv; i += blockDim.x) {
-    const int r = (i * 8) / D;
-    const int c = (i * 8) % D;
-    s16x8 val{};
-    if (r < rows)
-      val = *reinterpret_cast<const s16x8*>(g + (long)r * rs + c);
-    *reinterpret_cast<s16x8*>(s + (long)r * ld + c) = val;
-  }
-}
-
-// stage transposed: global [rows x D] (row stride rs) -> LDS [D x ld]
-__device__ __forceinline__ void stage_tile_T(const bf16* g, long rs, bf16* s,
-                                             int rows, int rpad, int D,
-                                             int ld) {
-  for (int i = threadIdx.x; i < rpad * D / 8; i += blockDim.x) {
-    const int r = (i * 8) / D;
-    const int c0 = (i * 8) % D;
-    s16x8 val{};
-    if (r < rows)
-      val = *reinterpret_cast<const s16x8*>(g + (long)r * rs + c0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      s[(long)(c0 + e) * ld + r] = reinterpret_cast<const bf16*>(&val)[e];
-  }
-}
 
 // ---------------------------------------------------------------------
 // forward

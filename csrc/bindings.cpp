@@ -84,6 +84,25 @@ std::vector<at::Tensor> attn_bwd_qkv(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, double, double,
                                      c10::optional<at::Tensor>);
+// attention_tiled.hip
+std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       double, double,
+                                       c10::optional<at::Tensor>);
+std::vector<at::Tensor> attn_tiled_bwd(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&, double, double,
+                                       c10::optional<at::Tensor>);
+std::vector<at::Tensor> attn_tiled_fwd_qkv(const at::Tensor&,
+                                           const at::Tensor&, double, double,
+                                           c10::optional<at::Tensor>);
+std::vector<at::Tensor> attn_tiled_bwd_qkv(const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&, double, double,
+                                           c10::optional<at::Tensor>);
 // tener.hip
 std::vector<at::Tensor> tener_attn_fwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
@@ -143,6 +162,10 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
   m.def("attn_bwd_qkv", &attn_bwd_qkv);
+  m.def("attn_tiled_fwd", &attn_tiled_fwd);
+  m.def("attn_tiled_bwd", &attn_tiled_bwd);
+  m.def("attn_tiled_fwd_qkv", &attn_tiled_fwd_qkv);
+  m.def("attn_tiled_bwd_qkv", &attn_tiled_bwd_qkv);
   m.def("tener_attn_fwd", &tener_attn_fwd);
   m.def("tener_attn_bwd", &tener_attn_bwd);
   m.def("mfma_probe", &mfma_probe);

@@ -17,7 +17,7 @@ OUT_DIR = os.path.join(REPO, "chinesener_amd", "ops")
 BUILD = os.path.join(REPO, "build")
 
 HIP_SOURCES = ["elementwise.hip", "crf.hip", "softlexicon.hip", "adam.hip",
-               "attention.hip", "tener.hip", "lstm.hip", "probe.hip",
+               "attention.hip", "attention_tiled.hip", "tener.hip", "lstm.hip", "probe.hip",
                "wgrad.hip", "gemm_nt.hip", "embed.hip"]
 CPP_SOURCES = ["bindings.cpp"]
 
@@ -56,8 +56,9 @@ def build(verbose: bool = True) -> str:
         src_path = os.path.join(CSRC, src)
         if (os.path.exists(obj)
                 and os.path.getmtime(obj) > os.path.getmtime(src_path)
-                and os.path.getmtime(obj) > os.path.getmtime(
-                    os.path.join(CSRC, "common.h"))):
+                and all(os.path.getmtime(obj) > os.path.getmtime(
+                    os.path.join(CSRC, h))
+                    for h in os.listdir(CSRC) if h.endswith(".h"))):
             continue
         cmd = ["hipcc", "--offload-arch=gfx950", "-c", src_path, "-o", obj] \
             + common + inc_flags
