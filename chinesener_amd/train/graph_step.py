@@ -25,6 +25,11 @@ from typing import Callable, Dict, Optional
 
 import torch
 
+from .. import ops
+from .optimizers import (AdamWeightDecay, fused_tail_enabled,
+                         kernel_ready_grad, publish_step_grads,
+                         take_step_coef)
+
 log = logging.getLogger("chinesener_amd")
 
 
@@ -43,6 +48,9 @@ class GraphedTrainStep:
         self.sig = None
         self.failed = False
         self._params = [p for p in model.parameters() if p.requires_grad]
+        # whether clip_fn consumes published grads (clip_gradients by
+        # global norm does): None until the first body has found out
+        self._fused_ok: Optional[bool] = None
 
     def _body(self):
         """One whole training step, capture-safe.
@@ -54,12 +62,44 @@ class GraphedTrainStep:
         loss or HSA aperture faults; reproduced and bisected on MI355X,
         scripts/debug/debug_capture_bisect.py: backward-capture arms corrupt,
         autograd.grad arms stay clean — the same reason upstream
-        make_graphed_callables captures via autograd.grad). Grads are
-        copied into persistent ``p.grad`` buffers so the cached
-        clip/optimizer meta blobs keep stable pointers."""
+        make_graphed_callables captures via autograd.grad).
+
+        ``autograd.grad`` returns fresh tensors, so nothing that reads
+        grads may keep their addresses in a cached device blob. On the
+        fused tail (GPU, HIP extension, AdamWeightDecay in graph-lr
+        mode, no data parallelism, CHINESENER_FUSED_TAIL not ``off``)
+        the grads are never copied: they are published on the model,
+        ``clip_gradients`` reduces them to sumsq and the clip factor,
+        and ``AdamWeightDecay.step`` receives them with that factor —
+        the kernels take the grad addresses as by-value arguments, which
+        capture bakes into the graph nodes. ``p.grad`` stays unallocated
+        (only the very first body, a warmup pass of ``try_capture``,
+        fills it once and frees it: that is where it finds out whether
+        ``clip_fn`` takes published grads at all).
+        ``grads`` stays referenced until the AdamW launch is recorded.
+
+        Everywhere else (CPU, other optimizers, a clip_fn that does not
+        clip by global norm through ``clip_gradients``, data parallelism
+        whose buckets read ``p.grad``) grads are copied into persistent
+        ``p.grad`` buffers so the cached clip/optimizer meta blobs keep
+        stable pointers."""
         out = self.model(self.cast(self.static))
         grads = torch.autograd.grad(out.loss, self._params,
                                     allow_unused=True)
+        fused = self._fused_tail()
+        if fused:
+            with torch.no_grad():
+                grads = [kernel_ready_grad(g, p)
+                         for g, p in zip(grads, self._params)]
+        if fused and self._fused_ok:
+            publish_step_grads(self.model, self._params, grads)
+            self.clip_fn(self.model)
+            handed = take_step_coef(self.model)
+            if handed is None:
+                raise RuntimeError("clip_fn stopped taking published grads")
+            self.opt.hand_grads(*handed)
+            self.opt.step()
+            return out.loss
         with torch.no_grad():
             for p, g in zip(self._params, grads):
                 if p.grad is None:
@@ -72,9 +112,30 @@ class GraphedTrainStep:
             # autograd.grad fires no post-accumulate hooks: run the
             # bucketed all-reduce explicitly (recorded into the graph)
             self.dp.reduce_in_graph()
+        if fused:
+            # first body (try_capture's warmup, before the capture): p.grad
+            # is filled as well, so a clip_fn that knows nothing of
+            # published grads has clipped the real thing and this step
+            # is right either way; what it did decides the later bodies
+            publish_step_grads(self.model, self._params, grads)
         self.clip_fn(self.model)
+        if fused:
+            handed = take_step_coef(self.model)
+            self._fused_ok = handed is not None
+            if handed is not None:
+                self.opt.hand_grads(*handed)
+                for p in self._params:
+                    p.grad = None    # not needed again
         self.opt.step()
         return out.loss
+
+    def _fused_tail(self) -> bool:
+        return (self._fused_ok is not False and self.dp is None
+                and fused_tail_enabled()
+                and isinstance(self.opt, AdamWeightDecay)
+                and self.opt.lr_dev is not None
+                and ops.ext_available()
+                and all(p.is_cuda for p in self._params))
 
     def _signature(self, batch):
         return tuple(sorted((k, tuple(v.shape), str(v.dtype))
@@ -175,6 +236,8 @@ class GraphedTrainStep:
             self.opt._meta_cache = {}
         if hasattr(self.model, "_clip_meta"):
             self.model._clip_meta = None
+        if hasattr(self.model, "_sumsq_meta"):
+            self.model._sumsq_meta = None
 
     def matches(self, batch) -> bool:
         return self.graph is not None and self.sig == self._signature(batch)

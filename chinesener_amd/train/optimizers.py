@@ -16,11 +16,33 @@ K16); CPU uses torch foreach ops with identical math.
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
 from .. import ops
+
+
+def fused_tail_enabled() -> bool:
+    """CHINESENER_FUSED_TAIL=off (read at call time) restores the
+    copy -> sumsq -> scale -> adam sequence in the graphed step."""
+    return os.environ.get("CHINESENER_FUSED_TAIL", "") != "off"
+
+
+def kernel_ready_grad(g: Optional[torch.Tensor], p: torch.Tensor
+                      ) -> Optional[torch.Tensor]:
+    """The grad as the by-value kernels need it: p's dtype, contiguous and
+    16-byte aligned for the vector loads. One that is not goes through a
+    per-tensor copy; None (no gradient) stays None. Shapes are static
+    under capture, so the choice is stable from replay to replay."""
+    if g is None:
+        return None
+    if g.dtype != p.dtype or not g.is_contiguous():
+        g = g.to(p.dtype).contiguous()
+    if g.data_ptr() % 16:
+        g = g.clone()
+    return g
 
 
 def _no_decay(name: str) -> bool:
@@ -76,15 +98,32 @@ class AdamWeightDecay(torch.optim.Optimizer):
         # device-side base LR (hipGraph-captured steps: the schedule
         # writes this scalar outside the graph, the fused kernel reads it)
         self.lr_dev: Optional[torch.Tensor] = None
+        # grads handed over for ONE step by GraphedTrainStep (see
+        # hand_grads); None: read p.grad as usual
+        self._handed = None
 
     def enable_graph_lr(self, device) -> torch.Tensor:
         self.lr_dev = torch.ones(1, dtype=torch.float32, device=device)
         self._meta_cache = {}
         return self.lr_dev
 
+    def hand_grads(self, params, grads, coef: Optional[torch.Tensor]):
+        """Give the next ``step()`` its gradients directly instead of
+        through ``p.grad``: ``grads[i]`` (kernel_ready_grad output, or
+        None for "no gradient" = zero) belongs to ``params[i]``, and
+        ``coef`` is the 1-element device clip factor the fused kernel
+        multiplies in as it loads them. Graph mode (lr_dev) on the GPU
+        only; the caller keeps ``grads`` alive until ``step()`` returns."""
+        if self.lr_dev is None or not ops.ext_available():
+            raise RuntimeError("hand_grads needs graph-lr mode and the "
+                               "HIP extension")
+        self._handed = ({id(p): g for p, g in zip(params, grads)}, coef)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        handed, self._handed = self._handed, None
+        gmap, coef = handed if handed is not None else (None, None)
         # fused bins by param dtype: bf16 params carry an fp32 master copy
         # (pure-bf16 training mode — no autocast weight casts per step)
         fused = {torch.bfloat16: [], torch.float32: []}
@@ -94,12 +133,14 @@ class AdamWeightDecay(torch.optim.Optimizer):
         split_groups = []
         for group in self.param_groups:
             for dt in (torch.float32, torch.bfloat16):
-                params = [p for p in group["params"]
-                          if p.grad is not None and p.dtype == dt]
+                params = [p for p in group["params"] if p.dtype == dt
+                          and (p.grad is not None if gmap is None
+                               else id(p) in gmap)]
                 if params:
                     split_groups.append((group, params))
         for group, params in split_groups:
-            grads = [p.grad for p in params]
+            grads = ([p.grad for p in params] if gmap is None
+                     else [gmap[id(p)] for p in params])
             states = [self.state[p] for p in params]
             for p, s in zip(params, states):
                 if "m" not in s:
@@ -123,9 +164,13 @@ class AdamWeightDecay(torch.optim.Optimizer):
             if params[0].is_cuda and ops.ext_available():
                 masters = ([s["master"] for s in states]
                            if params[0].dtype == torch.bfloat16 else [])
+                if gmap is None:
+                    grads = [g.contiguous() for g in grads]
                 fused[params[0].dtype].append(
-                    (params, [g.contiguous() for g in grads], masters, ms, vs,
+                    (params, grads, masters, ms, vs,
                      [lr] * len(params), [wd] * len(params)))
+            elif gmap is not None:
+                raise RuntimeError("handed grads need GPU params")
             elif params[0].dtype == torch.bfloat16:
                 # eager master-weight path (CPU/debug)
                 for p, g, s in zip(params, grads, states):
@@ -156,7 +201,23 @@ class AdamWeightDecay(torch.optim.Optimizer):
             eps = self.param_groups[0]["eps"]
             cat = [sum((f[i] for f in bins), []) for i in range(7)]
             ext = ops.get_ext()
-            if self.lr_dev is None:
+            if gmap is not None:
+                # grad addresses travel as kernel arguments, so the cached
+                # blob holds only what is stable (p, master, m, v, n, lr
+                # scale, wd) and is keyed by those tensors alone
+                sig = tuple(t.data_ptr()
+                            for t in cat[0] + cat[2] + cat[3] + cat[4])
+                cache = self._meta_cache.get(("tab", dtype))
+                if cache is None or cache[0] != sig:
+                    blob, info = ext.adamw_build_meta(
+                        cat[0], [], cat[2], cat[3], cat[4], cat[5], cat[6])
+                    total, n, isbf = info.tolist()
+                    cache = (sig, blob, total, n, bool(isbf))
+                    self._meta_cache[("tab", dtype)] = cache
+                ext.multi_tensor_adamw_tab_run(
+                    cache[1], cache[2], cache[3], cache[4], cat[0], cat[1],
+                    b1, b2, eps, self.lr_dev, coef)
+            elif self.lr_dev is None:
                 ext.multi_tensor_adamw(cat[0], cat[1], cat[2], cat[3],
                                        cat[4], cat[5], cat[6],
                                        b1, b2, eps, None)
@@ -230,22 +291,78 @@ class LrSchedule:
         return lr
 
 
+def _sumsq_coef(model: torch.nn.Module, like: List[torch.Tensor],
+                grads: List[Optional[torch.Tensor]],
+                max_norm: float) -> torch.Tensor:
+    """{sumsq, coef} of ``grads`` as one 2-element fp32 device tensor:
+    balanced sum-of-squares kernel + one-block finisher, no atomics, no
+    scalar torch kernels. ``like[i]`` gives the size and dtype of entry i
+    (its grad may be None = zero). The chunk list depends on those only,
+    so it is cached on the model; the grad addresses travel by value."""
+    ext = ops.get_ext()
+    key = tuple((t.numel(), t.dtype) for t in like)
+    sm = getattr(model, "_sumsq_meta", None)
+    if sm is None or sm[0] != key:
+        numels = [k[0] for k in key]
+        isbf = [int(k[1] == torch.bfloat16) for k in key]
+        sm = (key, ext.sumsq_build_chunks(numels, isbf, like[0]), numels,
+              isbf)
+        model._sumsq_meta = sm
+    return ext.multi_tensor_sumsq_coef_run(sm[1], sm[2], sm[3], grads,
+                                           max_norm)
+
+
+def publish_step_grads(model: torch.nn.Module, params, grads) -> None:
+    """GraphedTrainStep's hand-off: the step's gradients, straight from
+    ``autograd.grad`` (through kernel_ready_grad), for the next
+    ``clip_gradients(model, ...)`` to pick up instead of ``p.grad``."""
+    model._step_grads = (list(params), list(grads))
+    model._step_coef = None
+
+
+def take_step_coef(model: torch.nn.Module):
+    """After the clip call: ``(params, grads, coef)`` if clip_gradients
+    consumed the published grads by global norm, else None with the
+    publication withdrawn (the caller then fills ``p.grad``)."""
+    pub = getattr(model, "_step_grads", None)
+    coef = getattr(model, "_step_coef", None)
+    model._step_grads = None
+    model._step_coef = None
+    if pub is None or coef is None:
+        return None
+    return pub[0], pub[1], coef
+
+
 def clip_gradients(model: torch.nn.Module, family: str,
                    max_norm: float = 1.0) -> Optional[torch.Tensor]:
     """bert/transformer: clip_by_global_norm 1.0 (:315,334); custom:
     clip_by_value +-5 (:379-390).
 
-    GPU path is fully device-side (fused multi-tensor sumsq + scale, no
-    host sync in the step loop); returns the squared-norm tensor."""
+    GPU path is fully device-side (multi-tensor sumsq + finisher + scale,
+    no host sync in the step loop); returns the squared-norm tensor.
+
+    When GraphedTrainStep has published the step's grads
+    (publish_step_grads) and the family clips by global norm, only sumsq
+    and coef are computed from them: nothing is scaled here, the fused
+    AdamW applies coef as it loads each grad."""
+    pub = getattr(model, "_step_grads", None)
+    if pub is not None and getattr(model, "_step_coef", None) is None \
+            and family in ("bert", "transformer"):
+        out = _sumsq_coef(model, pub[0], pub[1], max_norm)
+        model._step_coef = out[1:2]
+        return out[0:1]
     if family in ("bert", "transformer"):
         ps = [p for p in model.parameters() if p.grad is not None]
         if not ps:
             return None
+        use_ext = ps[0].grad.is_cuda and ops.ext_available()
         for p in ps:            # scale must hit the real grad storage
             if not p.grad.is_contiguous():
                 p.grad = p.grad.contiguous()
+            if use_ext and p.grad.data_ptr() % 16:
+                p.grad = p.grad.clone()   # vector loads need alignment
         grads = [p.grad for p in ps]
-        if grads[0].is_cuda and ops.ext_available():
+        if use_ext:
             ext = ops.get_ext()
             # cached device meta blob: capture-safe (no H2D in the step);
             # pointer signature invalidates when grads are reallocated
@@ -255,12 +372,9 @@ def clip_gradients(model: torch.nn.Module, family: str,
                 blob, info = ext.norm_build_meta(grads)
                 cm = (sig, blob, int(info[0]))
                 model._clip_meta = cm
-            out = torch.zeros(1, dtype=torch.float32, device=grads[0].device)
-            sumsq = ext.multi_tensor_sumsq_run(cm[1], cm[2], out)
-            norm = sumsq.sqrt()
-            coef = (max_norm / (norm + 1e-6)).clamp(max=1.0)
-            ext.multi_tensor_scale_run(cm[1], cm[2], coef)
-            return sumsq
+            out = _sumsq_coef(model, grads, grads, max_norm)
+            ext.multi_tensor_scale_run(cm[1], cm[2], out[1:2])
+            return out[0:1]
         return torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
     torch.nn.utils.clip_grad_value_(model.parameters(), 5.0)
     return None

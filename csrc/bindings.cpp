@@ -68,6 +68,19 @@ void multi_tensor_adamw_run(const at::Tensor&, long, long, bool, double,
 std::vector<at::Tensor> norm_build_meta(std::vector<at::Tensor>);
 at::Tensor multi_tensor_sumsq_run(const at::Tensor&, long, const at::Tensor&);
 void multi_tensor_scale_run(const at::Tensor&, long, const at::Tensor&);
+void multi_tensor_adamw_tab_run(const at::Tensor&, long, long, bool,
+                                std::vector<at::Tensor>,
+                                std::vector<c10::optional<at::Tensor>>, double,
+                                double, double, c10::optional<at::Tensor>,
+                                c10::optional<at::Tensor>);
+long grad_table_slots();
+long sumsq_chunk_elems();
+at::Tensor sumsq_build_chunks(std::vector<long>, std::vector<long>,
+                              const at::Tensor&);
+at::Tensor multi_tensor_sumsq_coef_run(const at::Tensor&, std::vector<long>,
+                                       std::vector<long>,
+                                       std::vector<c10::optional<at::Tensor>>,
+                                       double);
 // attention.hip
 std::vector<at::Tensor> attn_fwd(const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, const at::Tensor&, double,
@@ -158,6 +171,11 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("norm_build_meta", &norm_build_meta);
   m.def("multi_tensor_sumsq_run", &multi_tensor_sumsq_run);
   m.def("multi_tensor_scale_run", &multi_tensor_scale_run);
+  m.def("multi_tensor_adamw_tab_run", &multi_tensor_adamw_tab_run);
+  m.def("sumsq_build_chunks", &sumsq_build_chunks);
+  m.def("multi_tensor_sumsq_coef_run", &multi_tensor_sumsq_coef_run);
+  m.def("grad_table_slots", &grad_table_slots);
+  m.def("sumsq_chunk_elems", &sumsq_chunk_elems);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
