@@ -78,11 +78,10 @@ class BertLayer(nn.Module):
 
     def forward(self, x, mask, lens):
         B, L, H = x.shape
-        qkv = ops.linear(x, self.qkv.weight, self.qkv.bias) \
-            .reshape(B, L, 3, self.n_heads, self.head_dim)
-        ctx = ops.attention_qkv(qkv, mask=mask, lens=lens,
-                                p_drop=self.p_attn_drop,
-                                training=self.training).reshape(B, L, H)
+        ctx = ops.linear_attention_qkv(
+            x, self.qkv.weight, self.qkv.bias, self.n_heads, mask=mask,
+            lens=lens, p_drop=self.p_attn_drop,
+            training=self.training).reshape(B, L, H)
         x = ops.linear_dropout_add_layernorm(
             ctx, self.attn_out.weight, self.attn_out.bias, x, self.ln1_w,
             self.ln1_b, self.eps, self.p_drop, self.training)

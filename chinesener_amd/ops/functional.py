@@ -578,6 +578,71 @@ def attention_qkv(qkv, mask: Optional[torch.Tensor] = None,
     return out.transpose(1, 2)
 
 
+class _LinearAttentionQkvFn(torch.autograd.Function):
+    """attention_qkv(x @ w^T + b) as one node on the full-LDS path: the
+    attention backward kernel also emits the column sum of dqkv, which is
+    the projection's bias grad, so backward needs no colsum pass."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, lens, n_heads, scale, keep):
+        B, L = x.shape[0], x.shape[1]
+        qkv = _linear_fwd(x, w, b).reshape(B, L, 3, n_heads, -1).contiguous()
+        seed = None
+        if keep < 1.0:
+            ctr = _rng_counter_for(x.device)
+            seed = ctr.clone()
+            get_ext().bump_counter(ctr)
+        out, lse = get_ext().attn_fwd_qkv(qkv, lens, scale, keep, seed)
+        ctx.save_for_backward(x, w, b, qkv, out, lse, lens,
+                              seed if seed is not None else torch.zeros(0))
+        ctx.scale = scale
+        ctx.keep = keep
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, b, qkv, out, lse, lens, seed = ctx.saved_tensors
+        dqkv, dbias = get_ext().attn_bwd_qkv_dbias(
+            dout.contiguous(), qkv, out, lse, lens, ctx.scale, ctx.keep,
+            seed if seed.numel() else None, b)
+        dyf = dqkv.reshape(-1, w.shape[0])
+        dx = _linear_dgrad(dyf, x, w)
+        dw = _linear_wgrad(dyf, x, w)
+        return dx, dw, dbias, None, None, None, None
+
+
+def linear_attention_qkv(x, weight, bias, n_heads: int,
+                         mask: Optional[torch.Tensor] = None,
+                         lens: Optional[torch.Tensor] = None,
+                         p_drop: float = 0.0, training: bool = False):
+    """attention_qkv(linear(x).reshape(B, L, 3, n_heads, D)) -> [B,L,H,D]:
+    the fused QKV projection and self-attention of a BERT layer. Same
+    kernels forward, same RNG counter snapshot and single bump as the
+    composition below; on the full-LDS attention path (uniform bf16 on
+    GPU, no autocast, L <= 160, D in {32, 64}) the fused node takes the
+    projection's bias grad from the attention backward kernel."""
+    B, L = x.shape[0], x.shape[1]
+    D = weight.shape[0] // (3 * n_heads)
+    if (bias is not None and hip_enabled(x) and x.dtype == torch.bfloat16
+            and weight.dtype == x.dtype and bias.dtype == x.dtype
+            and not torch.is_autocast_enabled()
+            and D in (32, 64) and weight.shape[0] == 3 * n_heads * D
+            and _attn_path(L, D, x.dtype, True) == "lds"):
+        keep = 1.0 - p_drop if (training and p_drop > 0) else 1.0
+        if os.environ.get("CHINESENER_NO_ATTN_DROP") == "1":
+            keep = 1.0
+        if lens is None:
+            lens = (mask.long().sum(1) if mask is not None
+                    else torch.full((B,), L, dtype=torch.long,
+                                    device=x.device))
+        return _LinearAttentionQkvFn.apply(
+            x, weight, bias, lens.to(torch.int32), n_heads,
+            1.0 / math.sqrt(D), float(keep))
+    qkv = linear(x, weight, bias).reshape(B, L, 3, n_heads, -1)
+    return attention_qkv(qkv, mask=mask, lens=lens, p_drop=p_drop,
+                         training=training)
+
+
 class _TenerAttentionFn(torch.autograd.Function):
     """Kernel contract: qu = q+u, qv = q+v precomputed (u/v grads are
     reductions of dqu/dqv handled by autograd outside this Function)."""

@@ -15,16 +15,25 @@ __device__ __forceinline__ bfrag lds_frag(const bf16* base, int i0, int ld,
                                          k0 + ((l >> 4) << 3));
 }
 
-// B operand from a ROW-major [K][N] LDS buffer (per-element reads)
-__device__ __forceinline__ bfrag lds_fragB_rowmajor(const bf16* base, int k0,
-                                                    int ld, int n0) {
+// 16x16x32 operand read TRANSPOSED from a row-major [K][N] LDS image with
+// two ds_read_b64_tr_b16: element j of lane (g = l>>4, i = l&15) is
+// base[k0 + 8g + j][column i of the group's 16 columns]. Lane 4q+p of a
+// group addresses row q of a 4-row block, 4 contiguous columns starting at
+// `col` -- the caller picks `col` per lane (n0 + 4p for 16 natural columns;
+// any other 4-column chunk per p permutes the operand's row/column index).
+// Needs EXEC all ones, 8-byte aligned addresses (ld % 4 == 0, col % 4 == 0)
+// and every lane's address inside the padded tile.
+__device__ __forceinline__ bfrag lds_frag_tr(const bf16* base, int k0, int ld,
+                                             int col) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   const int l = threadIdx.x & (WAVE - 1);
-  bfrag b;
-#pragma unroll
-  for (int e = 0; e < 8; ++e)
-    reinterpret_cast<bf16*>(&b)[e] =
-        base[(long)(k0 + ((l >> 4) << 3) + e) * ld + n0 + (l & 15)];
-  return b;
+  const bf16* a = base + (long)(k0 + ((l >> 4) << 3) + ((l & 15) >> 2)) * ld +
+                  col;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a);
+  const s16x4 hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 4 * ld));
+  const s16x8 f = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bfrag, f);
 }
 
 __device__ __forceinline__ cfrag mfma16(bfrag a, bfrag b, cfrag c) {

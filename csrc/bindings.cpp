@@ -97,6 +97,10 @@ std::vector<at::Tensor> attn_bwd_qkv(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, double, double,
                                      c10::optional<at::Tensor>);
+std::vector<at::Tensor> attn_bwd_qkv_dbias(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, double, double,
+    c10::optional<at::Tensor>, const at::Tensor&);
 // attention_tiled.hip
 std::vector<at::Tensor> attn_tiled_fwd(const at::Tensor&, const at::Tensor&,
                                        const at::Tensor&, const at::Tensor&,
@@ -180,6 +184,7 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
   m.def("attn_bwd_qkv", &attn_bwd_qkv);
+  m.def("attn_bwd_qkv_dbias", &attn_bwd_qkv_dbias);
   m.def("attn_tiled_fwd", &attn_tiled_fwd);
   m.def("attn_tiled_bwd", &attn_tiled_bwd);
   m.def("attn_tiled_fwd_qkv", &attn_tiled_fwd_qkv);
