@@ -809,7 +809,7 @@ def bilstm(x, w_ih_f, w_hh_f, b_f, w_ih_b, w_hh_b, b_b, lens,
            cell_clip: float = 0.0):
     """BiLSTM over padded [B,L,E] -> [B,L,2h].
 
-    HIP path: hidden <= 256 (W_hh LDS-resident up to 128, L2-streamed
+    HIP path: hidden <= 256 (W_hh register-resident up to 128, L2-streamed
     above); non-multiple-of-32 hidden sizes are zero-padded — padded
     units stay exactly 0 through the recurrence (sigmoid(0)*act(0)
     structure), so sliced outputs and grads are exact. Larger sizes run
