@@ -46,6 +46,12 @@ std::vector<at::Tensor> crf_fwd(const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, const at::Tensor&);
 at::Tensor crf_viterbi(const at::Tensor&, const at::Tensor&,
                        const at::Tensor&);
+// crf_wide.hip (T <= 64, L <= 512): reached through crf_fwd / crf_viterbi,
+// which route to it every shape the narrow kernels cannot launch
+std::vector<at::Tensor> crf_wide_fwd(const at::Tensor&, const at::Tensor&,
+                                     const at::Tensor&, const at::Tensor&);
+at::Tensor crf_wide_viterbi(const at::Tensor&, const at::Tensor&,
+                            const at::Tensor&);
 // softlexicon.hip
 at::Tensor softlexicon_fwd(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&);

@@ -385,19 +385,30 @@ __global__ void crf_viterbi_kernel(const float* __restrict__ emis,
 }
 
 // ===================================================================== host
+// crf_wide.hip: 1 <= T <= 64, 1 <= L <= 512
+std::vector<at::Tensor> crf_wide_fwd(const at::Tensor&, const at::Tensor&,
+                                     const at::Tensor&, const at::Tensor&);
+at::Tensor crf_wide_viterbi(const at::Tensor&, const at::Tensor&,
+                            const at::Tensor&);
+
 std::vector<at::Tensor> crf_fwd(const at::Tensor& emissions,
                                 const at::Tensor& tags, const at::Tensor& lens,
                                 const at::Tensor& trans) {
   CHECK_CUDA_CONTIG(emissions);
   const int B = emissions.size(0), L = emissions.size(1), T = emissions.size(2);
-  TORCH_CHECK(T <= TMAX, "CRF: label_size > ", TMAX);
-  auto ll = at::empty({B}, emissions.options());
-  auto demis = at::zeros_like(emissions);
-  auto dtrans = at::zeros({B, T, T}, emissions.options());
   const int nw = 4;
   const size_t smem4 = T16 * T16 * sizeof(float) +
                        (size_t)nw * 4 * L * T * sizeof(float);
-  if (T <= T16 && smem4 <= 160 * 1024) {
+  const size_t smem = TMAX * TMAX * sizeof(float) +
+                      (size_t)nw * L * T * sizeof(float);
+  const bool x4 = T <= T16 && smem4 <= 160 * 1024;
+  // shapes neither kernel of this file can launch go to crf_wide.hip
+  if (!x4 && (T > TMAX || smem > 160 * 1024))
+    return crf_wide_fwd(emissions, tags, lens, trans);
+  auto ll = at::empty({B}, emissions.options());
+  auto demis = at::zeros_like(emissions);
+  auto dtrans = at::zeros({B, T, T}, emissions.options());
+  if (x4) {
     // 4 sequences per wave (16 per block): 4x the active lanes
     hipLaunchKernelGGL(crf_fwd_kernel_x4, dim3((B + nw * 4 - 1) / (nw * 4)),
                        dim3(nw * WAVE), smem4, cur_stream(emissions),
@@ -408,9 +419,6 @@ std::vector<at::Tensor> crf_fwd(const at::Tensor& emissions,
     HIP_CHECK_LAST();
     return {ll, demis, dtrans};
   }
-  const size_t smem = TMAX * TMAX * sizeof(float) +
-                      (size_t)nw * L * T * sizeof(float);
-  TORCH_CHECK(smem <= 160 * 1024, "CRF fwd: LDS overflow (L*T too big)");
   hipLaunchKernelGGL(crf_fwd_kernel, dim3((B + nw - 1) / nw), dim3(nw * WAVE),
                      smem, cur_stream(emissions),
                      emissions.data_ptr<float>(), tags.data_ptr<int>(),
@@ -425,11 +433,14 @@ at::Tensor crf_viterbi(const at::Tensor& emissions, const at::Tensor& lens,
                        const at::Tensor& trans) {
   CHECK_CUDA_CONTIG(emissions);
   const int B = emissions.size(0), L = emissions.size(1), T = emissions.size(2);
-  TORCH_CHECK(T <= TMAX, "CRF: label_size > ", TMAX);
-  auto pred = at::zeros({B, L}, emissions.options().dtype(at::kInt));
   const int nw = 4;
   const size_t smem4 = T16 * T16 * sizeof(float) + (size_t)nw * 4 * L * T16;
-  if (T <= T16 && smem4 <= 160 * 1024) {
+  const size_t smem = TMAX * TMAX * sizeof(float) + (size_t)nw * L * TMAX;
+  const bool x4 = T <= T16 && smem4 <= 160 * 1024;
+  if (!x4 && (T > TMAX || smem > 160 * 1024))
+    return crf_wide_viterbi(emissions, lens, trans);
+  auto pred = at::zeros({B, L}, emissions.options().dtype(at::kInt));
+  if (x4) {
     hipLaunchKernelGGL(crf_viterbi_kernel_x4,
                        dim3((B + nw * 4 - 1) / (nw * 4)), dim3(nw * WAVE),
                        smem4, cur_stream(emissions),
@@ -438,8 +449,6 @@ at::Tensor crf_viterbi(const at::Tensor& emissions, const at::Tensor& lens,
     HIP_CHECK_LAST();
     return pred;
   }
-  const size_t smem = TMAX * TMAX * sizeof(float) + (size_t)nw * L * TMAX;
-  TORCH_CHECK(smem <= 160 * 1024, "CRF viterbi: LDS overflow");
   hipLaunchKernelGGL(crf_viterbi_kernel, dim3((B + nw - 1) / nw),
                      dim3(nw * WAVE), smem, cur_stream(emissions),
                      emissions.data_ptr<float>(), lens.data_ptr<int>(),
