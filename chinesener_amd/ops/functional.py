@@ -244,13 +244,13 @@ def _linear_dgrad(dyf, x, w):
     M, N = dyf.shape
     K = x.shape[-1]
     mode = _gemm_nt_mode()
-    bf16 = dyf.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+    bf16 = (dyf.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16)
 
-    # dx[M,K] = dy @ w == gemm_nt(dy[M,N], w^T[K,N]) — the transpose of
-    # the small weight (few MB) is part of the timed candidate, so the
-    # measured dispatch accounts for it
+    # dx[M,K] = dy[M,N] @ w[N,K]: gemm_nn reads the weight in its stored
+    # [out, in] layout (transposed LDS reads), so no copy of w is made
     def dx_ours():
-        return get_ext().gemm_nt(dyf, w.t().contiguous(), None, False)
+        return get_ext().gemm_nn(dyf.contiguous(), w.contiguous(), False)
 
     def dx_lib():
         return dyf @ w.to(dyf.dtype)
@@ -264,7 +264,8 @@ def _linear_dgrad(dyf, x, w):
 
 
 def _linear_wgrad(dyf, x, w):
-    """dW[N,K] = dy^T @ x == gemm_nt(dy^T[N,M], x^T[K,M]), in w's dtype."""
+    """dW[N,K] = dy^T @ x == gemm_tn(dy[M,N], x[M,K]), in w's dtype: both
+    activations are read as stored, split-K chosen by the extension."""
     M, N = dyf.shape
     K = x.shape[-1]
     x2 = x.reshape(-1, K)
@@ -272,8 +273,7 @@ def _linear_wgrad(dyf, x, w):
     bf16 = dyf.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
 
     def dw_ours():
-        return get_ext().gemm_nt(dyf.t().contiguous(),
-                                 x2.t().contiguous(), None, False)
+        return get_ext().gemm_tn(dyf.contiguous(), x2.contiguous(), 0, False)
 
     def dw_lib():
         return dyf.T @ x2

@@ -2,8 +2,9 @@
 // C[M, N] = A[M, K] @ B[N, K]^T (+ bias[N]) with both operands K-major
 // row-major — exactly torch's F.linear(x, w): A = activations, B = the
 // [out, in] weight. Both MFMA fragments read 8 contiguous bf16 along K,
-// so no transpose anywhere (the layout hipBLASLt calls NT and where the
-// in-tree wgrad TT kernels lose to Tensile).
+// so no transpose anywhere (the layout hipBLASLt calls NT). The backward
+// products, whose contraction index is a row index in memory (gemm_tn for
+// wgrad, gemm_nn for dgrad), are in the second half of this file.
 //
 // Structure (guide §5 "step-3" ladder stage, measured 874-912 TF/s at
 // 4096^3 on this chip): 128x128 output tile per 256-thread workgroup
@@ -202,4 +203,301 @@ at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b,
     launch_gemm_nt<bf16>(a, b, bias, out, M, N, K);
   HIP_CHECK_LAST();
   return out;
+}
+
+// ===================================================================
+// Transposed-operand variants for the backward products:
+//   gemm_tn: C[M, N] = A[T, M]^T @ B[T, N]   (wgrad: dW = dy^T @ x)
+//   gemm_nn: C[M, N] = A[M, K]   @ B[K, N]   (dgrad: dx = dy @ w)
+// An operand whose contraction index is its ROW index in memory
+// ("k-strided") is staged exactly like the k-major one -- coalesced full
+// rows, glds width 16, lane-linear image, XOR on the source address --
+// as a [BK = 64 rows of k][128 columns] tile with 256-byte rows, and is
+// consumed column-wise with ds_read_b64_tr_b16 (two per fragment), so
+// there is no transpose pass anywhere. The k-major A operand of gemm_nn
+// reuses stage_tile/frag above. Both reads give lane (g, i) the k
+// indices 8g .. 8g+7 of row/column i, so the two kinds mix freely.
+//
+// LDS image of a k-strided tile (guide T10 image (b)): byte offset of
+// 16-byte chunk ch of row r is 256 r + 16 (ch ^ X(r)),
+// X(r) = ((r & 3) << 2) | ((r >> 2) & 3). Bank check (bank = (a/4) % 64,
+// conflicts per 32-lane half): in one transposed read a half holds
+// groups g, g+1 = rows r0 + q and r0 + 8 + q (q = 0..3), chunks
+// {2m, 2m+1}; the slot is (2m | p>>1) ^ (q << 2) ^ {0, 2} (+1 for the
+// second read, rows + 4): 16 distinct slots, each split in two 8-byte
+// halves by p & 1 -> 32 lanes x 8 B cover the 256-byte bank row exactly
+// once. Both reads of a fragment are conflict-free.
+__device__ __forceinline__ int swz_ks(int row) {
+  return ((row & 3) << 2) | ((row >> 2) & 3);
+}
+
+// Stage one [BK][128] bf16 tile (rows k0.., columns c0.., row stride
+// `ld` elements) into lds: one glds-b128 per wave fills 4 rows.
+__device__ __forceinline__ void stage_tile_ks(const bf16* __restrict__ g,
+                                              long ld, long k0, long c0,
+                                              bf16* lds) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int lds_off = (t / WAVE) * 4096 + i * 1024 + (t % WAVE) * 16;
+    const int row = lds_off >> 8;            // 256 B per row
+    const int slot = (lds_off & 255) >> 4;   // 16-B slot in row
+    const long src = (k0 + row) * ld + c0 + (long)((slot ^ swz_ks(row)) << 3);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)(g + src),
+        (__attribute__((address_space(3))) void*)(lds + (lds_off >> 1)),
+        16, 0, 0);
+  }
+}
+
+// Element offset this lane supplies to the transposed read of the 4-row
+// block starting at row `r0` (multiple of 4), 16 columns from `c0`
+// (multiple of 16): lane 4q+p of a group -> row r0 + q, columns
+// c0 + 4p .. +3. The XOR can swap the two chunks of a 32-byte span, so
+// every lane goes through the image's own offset function.
+__device__ __forceinline__ int tr_off(int r0, int c0) {
+  const int l = threadIdx.x & (WAVE - 1);
+  const int row = r0 + ((l & 15) >> 2);
+  const int col = c0 + ((l & 3) << 2);
+  return (row << 7) + (((col >> 3) ^ swz_ks(row)) << 3) + (col & 7);
+}
+
+// 16x16x32 operand, lane (g, i) element j = tile[k0 + 8g + j][c0 + i],
+// from the two precomputed offsets (rows 8g.. and 8g+4..). Needs EXEC
+// all ones and a 16-byte aligned tile.
+__device__ __forceinline__ bfrag frag_tr(const bf16* tile, int off_lo,
+                                         int off_hi) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const s16x4 lo =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off_lo));
+  const s16x4 hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off_hi));
+  const s16x8 f = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bfrag, f);
+}
+
+// A_KMAJOR: A is [M, K] (gemm_nn) else [K, M] (gemm_tn); B is [K, N].
+// blockIdx covers tiles x split; split s contracts K-stages
+// [s nkt / split, (s+1) nkt / split) and writes slab s of C.
+template <bool A_KMAJOR, typename OT>
+__global__ __launch_bounds__(256, 2) void gemm_ks_kernel(
+    const bf16* __restrict__ A, const bf16* __restrict__ B,
+    OT* __restrict__ C,           // [split][M, N]
+    long M, long N, long K, int tiles_n, int tiles, int split) {
+  __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * BM * BK];
+  bf16* a_s = smem;                          // [2][8192]
+  bf16* b_s = smem + 2 * BM * BK;
+
+  const int nwg = gridDim.x;
+  int wg = blockIdx.x;
+  {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = wg & 7, idx = wg >> 3;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int s = wg / tiles, tile = wg - s * tiles;
+  const long m0 = (long)(tile / tiles_n) * BM;
+  const long n0 = (long)(tile % tiles_n) * BN;
+
+  const int wid = threadIdx.x / WAVE;
+  const int wr = (wid >> 1) * 64, wc = (wid & 1) * 64;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g8 = (lane >> 4) << 3;
+
+  int aoff[4][2], boff[4][2];                // kk = 0; kk adds 32 rows
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    aoff[i][0] = tr_off(g8, wr + i * 16);
+    aoff[i][1] = tr_off(g8 + 4, wr + i * 16);
+    boff[i][0] = tr_off(g8, wc + i * 16);
+    boff[i][1] = tr_off(g8 + 4, wc + i * 16);
+  }
+
+  cfrag acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = cfrag{0.f, 0.f, 0.f, 0.f};
+
+  const int nkt = (int)(K / BK);
+  const int kb = (int)((long)s * nkt / split);
+  const int ke = (int)((long)(s + 1) * nkt / split);
+
+  if (A_KMAJOR) stage_tile(A, K, m0, (long)kb * BK, a_s);
+  else stage_tile_ks(A, M, (long)kb * BK, m0, a_s);
+  stage_tile_ks(B, N, (long)kb * BK, n0, b_s);
+  __syncthreads();
+
+  // Per stage: read every fragment of the current tile, then issue the
+  // next tile's glds, then the 32 MFMAs. A transposed read issued while
+  // glds writes are in flight makes the compiler drain vmcnt first (it
+  // cannot tell the two LDS buffers apart), which would serialise the
+  // prefetch; in this order the only vmcnt(0) is the one at the barrier.
+  int buf = 0;
+  for (int kt = kb; kt < ke; ++kt) {
+    const bf16* at = a_s + buf * BM * BK;
+    const bf16* bt = b_s + buf * BM * BK;
+    bfrag af[BK / 32][4], bfr[BK / 32][4];
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        af[kk][i] = A_KMAJOR ? frag(at, wr + i * 16, kk * 32)
+                             : frag_tr(at + kk * 32 * 128, aoff[i][0],
+                                       aoff[i][1]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bfr[kk][j] = frag_tr(bt + kk * 32 * 128, boff[j][0], boff[j][1]);
+    }
+    if (kt + 1 < ke) {                       // prefetch next K-tile
+      const int nxt = buf ^ 1;
+      const long k1 = (long)(kt + 1) * BK;
+      if (A_KMAJOR) stage_tile(A, K, m0, k1, a_s + nxt * BM * BK);
+      else stage_tile_ks(A, M, k1, m0, a_s + nxt * BM * BK);
+      stage_tile_ks(B, N, k1, n0, b_s + nxt * BM * BK);
+    }
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = mfma16(af[kk][i], bfr[kk][j], acc[i][j]);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();                         // joins + drains prefetch
+    buf ^= 1;
+  }
+
+  OT* Cs = C + (long)s * M * N;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row0 = m0 + wr + i * 16 + ((lane >> 4) << 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long col = n0 + wc + j * 16 + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        from_f32(acc[i][j][r], &Cs[(row0 + r) * N + col]);
+    }
+  }
+}
+
+// out[i] = sum over slabs in slab order (fixed order: reproducible)
+template <typename OT>
+__global__ __launch_bounds__(256) void splitk_finish_kernel(
+    const float* __restrict__ part, OT* __restrict__ out, long n4,
+    long slab, int split) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  f32x4 acc = reinterpret_cast<const f32x4*>(part)[i];
+  for (int s = 1; s < split; ++s)
+    acc += reinterpret_cast<const f32x4*>(part + (long)s * slab)[i];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) from_f32(acc[e], &out[i * 4 + e]);
+}
+
+// Host split rule for gemm_tn (split == 0), from the measured per-shape
+// table in profiles/gemm_tn_r08.md: a workgroup wave is 512 resident
+// tiles (256 CUs x 2); cost = waves x stages per split, plus the
+// partial-slab traffic of the finisher counted in stage units.
+static int choose_split(long tiles, long nkt, long MN) {
+  static const int cand[] = {1, 2, 3, 4, 6, 8};
+  int best = 1;
+  double best_cost = 1e30;
+  for (int c : cand) {
+    if (c > nkt) break;
+    const double waves = (double)((tiles * c + 511) / 512);
+    const double stages = (double)((nkt + c - 1) / c);
+    // one stage of a resident pair ~0.7 us; slab write + read at ~6 TB/s
+    double cost = waves * stages * 0.7;
+    if (tiles * c < 256) cost *= 0.75;       // CUs not shared: faster stage
+    if (c > 1) cost += 2.0 + (double)c * MN * 8.0 / 6.0e6;
+    if (cost < best_cost) { best_cost = cost; best = c; }
+  }
+  return best;
+}
+
+template <bool A_KMAJOR>
+static at::Tensor launch_gemm_ks(const at::Tensor& a, const at::Tensor& b,
+                                 long M, long N, long K, int split,
+                                 bool fp32_out) {
+  const int tiles_n = (int)(N / BN), tiles = (int)((M / BM) * tiles_n);
+  auto out = at::empty({M, N}, a.options().dtype(
+                                   fp32_out ? at::kFloat : at::kBFloat16));
+  auto st = cur_stream(a);
+  const bf16* ap = (const bf16*)a.data_ptr();
+  const bf16* bp = (const bf16*)b.data_ptr();
+  if (split == 1) {
+    if (fp32_out)
+      hipLaunchKernelGGL((gemm_ks_kernel<A_KMAJOR, float>), dim3(tiles),
+                         dim3(256), 0, st, ap, bp, out.data_ptr<float>(), M,
+                         N, K, tiles_n, tiles, 1);
+    else
+      hipLaunchKernelGGL((gemm_ks_kernel<A_KMAJOR, bf16>), dim3(tiles),
+                         dim3(256), 0, st, ap, bp, (bf16*)out.data_ptr(), M,
+                         N, K, tiles_n, tiles, 1);
+    HIP_CHECK_LAST();
+    return out;
+  }
+  auto ws = at::empty({(long)split, M, N}, a.options().dtype(at::kFloat));
+  hipLaunchKernelGGL((gemm_ks_kernel<A_KMAJOR, float>),
+                     dim3((unsigned)(tiles * split)), dim3(256), 0, st, ap,
+                     bp, ws.data_ptr<float>(), M, N, K, tiles_n, tiles,
+                     split);
+  HIP_CHECK_LAST();
+  const long n4 = M * N / 4;
+  dim3 fgrid((unsigned)((n4 + 255) / 256));
+  if (fp32_out)
+    hipLaunchKernelGGL((splitk_finish_kernel<float>), fgrid, dim3(256), 0, st,
+                       ws.data_ptr<float>(), out.data_ptr<float>(), n4,
+                       M * N, split);
+  else
+    hipLaunchKernelGGL((splitk_finish_kernel<bf16>), fgrid, dim3(256), 0, st,
+                       ws.data_ptr<float>(), (bf16*)out.data_ptr(), n4,
+                       M * N, split);
+  HIP_CHECK_LAST();
+  return out;
+}
+
+// C = A^T @ B. A [T,M] bf16, B [T,N] bf16; split-K over T with fp32
+// partial slabs and a fixed-order finisher (split 1: direct; split 0:
+// host rule). out bf16 or fp32.
+at::Tensor gemm_tn(const at::Tensor& a, const at::Tensor& b, long split,
+                   bool fp32_out) {
+  CHECK_CUDA_CONTIG(a);
+  CHECK_CUDA_CONTIG(b);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 &&
+                  a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              "gemm_tn: 2-D bf16 operands");
+  const long T = a.size(0), M = a.size(1), N = b.size(1);
+  TORCH_CHECK(b.size(0) == T, "gemm_tn: T mismatch");
+  TORCH_CHECK(T > 0 && M > 0 && N > 0 && M % BM == 0 && N % BN == 0 &&
+                  T % BK == 0,
+              "gemm_tn: needs M%128==0, N%128==0, T%64==0 (got ", M, "x", N,
+              "x", T, ")");
+  const long nkt = T / BK;
+  TORCH_CHECK(split >= 0 && split <= 16 && split <= nkt,
+              "gemm_tn: split must be 0 (auto) or 1..min(16, T/64)");
+  if (split == 0) split = choose_split((M / BM) * (N / BN), nkt, M * N);
+  return launch_gemm_ks<false>(a, b, M, N, T, (int)split, fp32_out);
+}
+
+// C = A @ B. A [M,K] bf16, B [K,N] bf16 (a weight in its stored
+// [out, in] layout for dgrad); out bf16 or fp32.
+at::Tensor gemm_nn(const at::Tensor& a, const at::Tensor& b, bool fp32_out) {
+  CHECK_CUDA_CONTIG(a);
+  CHECK_CUDA_CONTIG(b);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 &&
+                  a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              "gemm_nn: 2-D bf16 operands");
+  const long M = a.size(0), K = a.size(1), N = b.size(1);
+  TORCH_CHECK(b.size(0) == K, "gemm_nn: K mismatch");
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 &&
+                  K % BK == 0,
+              "gemm_nn: needs M%128==0, N%128==0, K%64==0 (got ", M, "x", N,
+              "x", K, ")");
+  return launch_gemm_ks<true>(a, b, M, N, K, 1, fp32_out);
 }

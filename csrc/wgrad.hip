@@ -1,16 +1,18 @@
 // Weight-gradient GEMM (EXPERIMENTAL, not on the hot path): dW[N, K_in]
 // = dY^T @ X with dY [T, N], X [T, K_in] (T = tokens = contraction dim).
 //
-// Status: exact (unit-tested vs fp32 matmul) but ~185 TF/s vs
-// hipBLASLt's ~440 TF/s on the BERT wgrad shapes, so autograd keeps the
-// library GEMM. The contraction dim T is the row index of both global
-// operands, so MFMA K-contiguous fragments require a transpose
-// somewhere: v1 transposed during staging (scalar LDS stores dominated,
-// 110 TF/s); v2 (this code) stages [K][N]-oriented tiles with fully
-// vectorized copies and pays 8 scalar LDS reads per fragment instead
-// (185 TF/s). Beating Tensile here needs the assembly-grade
-// buffer_load + ds_write-swizzle transpose pipeline — future work;
-// kept as a measured baseline for it.
+// Status: superseded by gemm_tn in gemm_nt.hip, which stages the same
+// [K][N]-oriented tiles with global_load_lds and reads both MFMA operands
+// column-wise with ds_read_b64_tr_b16 (no transpose anywhere; 630-780
+// TF/s on the BERT wgrad shapes against the library's 420-510, see
+// profiles/gemm_tn_r08.md) and is what autograd dispatches to. These
+// kernels stay as the measured record of the attempts without the
+// transposed read, and because existing tests call them: the contraction
+// dim T is the row index of both global operands, so K-contiguous MFMA
+// fragments need a transpose somewhere: v1 transposed during staging
+// (scalar LDS stores dominated, 110 TF/s); v2 (this code) stages
+// [K][N]-oriented tiles with fully vectorized copies and pays 8 scalar
+// LDS reads per fragment instead (185 TF/s).
 //
 // Tile anatomy per workgroup (4 waves): 128x128 output tile, K split
 // across grid.z with fp32 atomic accumulation into a workspace.
