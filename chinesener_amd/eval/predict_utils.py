@@ -3,6 +3,7 @@ decode (reference tools/predict_utils.py:6-60 and tools/infer_utils.py:76-118
 behaviour, re-implemented)."""
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence
 
 SPECIAL_TAGS = ("[PAD]", "[CLS]", "[SEP]")
@@ -48,35 +49,71 @@ def process_prediction(row: Dict, idx2tag: Dict[int, str],
     return out
 
 
+def _bio_groups(tags: Sequence[str]):
+    """BIO grouping shared by the entity decoders: yields (type, start, end,
+    error) per span, end inclusive. A B- opens a span, an I- continues the
+    open one (or opens one when none is open), anything else closes it; an
+    I- of another type stays in the span and sets its error flag."""
+    cur_type, start, end, err = None, 0, 0, False
+    for i, tag in enumerate(tags):
+        if tag.startswith("B-"):
+            if cur_type is not None:
+                yield cur_type, start, end, err
+            cur_type, start, end, err = tag[2:], i, i, False
+        elif tag.startswith("I-"):
+            if cur_type is None:
+                cur_type, start, end, err = tag[2:], i, i, False
+            else:
+                if tag[2:] != cur_type:
+                    err = True
+                end = i
+        else:
+            if cur_type is not None:
+                yield cur_type, start, end, err
+            cur_type = None
+    if cur_type is not None:
+        yield cur_type, start, end, err
+
+
+def _surface(toks: Sequence[str], start: int, end: int, err: bool) -> str:
+    return "".join(toks[start:end + 1]) + ("[ERROR]" if err else "")
+
+
 def decode_prediction(tokens: Sequence[str], tags: Sequence[str]) -> Dict[str, List[str]]:
     """BIO tag sequence + tokens → {entity_type: [surface, ...]}; a B/I
     type mismatch inside one span marks the surface with '[ERROR]'
     (reference tools/predict_utils.py:6-36)."""
     entities: Dict[str, List[str]] = {}
-    cur_type, cur_toks, cur_err = None, [], False
-
-    def flush():
-        nonlocal cur_type, cur_toks, cur_err
-        if cur_type is not None and cur_toks:
-            surface = "".join(cur_toks) + ("[ERROR]" if cur_err else "")
-            entities.setdefault(cur_type, []).append(surface)
-        cur_type, cur_toks, cur_err = None, [], False
-
-    for tok, tag in zip(fix_tokens(tokens), tags):
-        if tag.startswith("B-"):
-            flush()
-            cur_type, cur_toks = tag[2:], [tok]
-        elif tag.startswith("I-"):
-            if cur_type is None:
-                cur_type, cur_toks = tag[2:], [tok]
-            else:
-                if tag[2:] != cur_type:
-                    cur_err = True
-                cur_toks.append(tok)
-        else:
-            flush()
-    flush()
+    toks = fix_tokens(tokens)
+    n = min(len(toks), len(tags))
+    for etype, start, end, err in _bio_groups(tags[:n]):
+        entities.setdefault(etype, []).append(_surface(toks, start, end, err))
     return entities
+
+
+def decode_prediction_scored(tokens: Sequence[str], tags: Sequence[str],
+                             span_a: Sequence[float], span_b: Sequence[float],
+                             offset: int = 0) -> List[Dict]:
+    """decode_prediction's spans, in order of appearance, each with its
+    confidence: [{"type", "text", "start", "end", "confidence"}] with
+    start/end token indices into ``tokens`` (end inclusive) and
+
+        confidence = exp(min(0, span_a[start+offset] + span_b[end+offset]))
+
+    span_a/span_b are one row of the model's span_scores; ``offset`` is the
+    shift between ``tokens`` and that row (1 when the row starts with
+    [CLS]). The confidence is the posterior that tokens start..end carry
+    exactly the decoded tags; it does not also require the entity to stop
+    at ``end``, so it is an upper bound on the strict BIO entity's."""
+    toks = fix_tokens(tokens)
+    n = min(len(toks), len(tags))
+    out = []
+    for etype, start, end, err in _bio_groups(tags[:n]):
+        logp = float(span_a[start + offset]) + float(span_b[end + offset])
+        out.append({"type": etype, "text": _surface(toks, start, end, err),
+                    "start": start, "end": end,
+                    "confidence": math.exp(min(0.0, logp))})
+    return out
 
 
 def extract_entity(tokens: Sequence[str], tags: Sequence[str]) -> Dict[str, set]:

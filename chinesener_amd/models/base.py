@@ -5,7 +5,7 @@ reference's ``build_graph(features, labels, params, is_training) ->
 model/bert_bilstm_crf_mtl.py:8-66)."""
 from __future__ import annotations
 
-from typing import Dict, NamedTuple, Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -16,6 +16,9 @@ class ModelOutput(NamedTuple):
     pred_ids: Optional[torch.Tensor] = None
     task_ids: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
+    # (span_a, span_b), fp64 [B,L]: log P(tags s..e as decoded) =
+    # span_a[s] + span_b[e]; filled only with compute_conf=True
+    span_scores: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
 
 class NerModel(nn.Module):
@@ -26,7 +29,10 @@ class NerModel(nn.Module):
         self.params = dict(params)
 
     def forward(self, features: Dict[str, torch.Tensor],
-                compute_pred: bool = False) -> ModelOutput:
+                compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
+        """compute_conf=True implies decoding and also fills
+        ModelOutput.span_scores (see ops.crf_path_posterior)."""
         raise NotImplementedError
 
 

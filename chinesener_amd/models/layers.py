@@ -117,6 +117,22 @@ class CRF(nn.Module):
     def decode(self, emissions, mask) -> torch.Tensor:
         return ops.crf_viterbi(emissions.float(), mask, self.transitions)
 
+    def decode_scored(self, emissions, mask):
+        """(pred, (span_a, span_b)): decode()'s tags plus the fp64 [B,L]
+        posterior arrays of that path, log P(tags s..e as decoded) =
+        span_a[s] + span_b[e]. It is the posterior of exactly these tags on
+        s..e, hence an upper bound on the strict BIO entity's."""
+        pred, span_a, span_b = ops.crf_decode_scored(
+            emissions.float(), mask, self.transitions)
+        return pred, (span_a, span_b)
+
+    def predict(self, emissions, mask, compute_pred: bool,
+                compute_conf: bool):
+        """The (pred, span_scores) pair a model's forward returns."""
+        if compute_conf:
+            return self.decode_scored(emissions, mask)
+        return (self.decode(emissions, mask) if compute_pred else None), None
+
 
 class TokenEmbedding(nn.Module):
     """Char/word embedding, optionally initialized from a pretrained matrix

@@ -31,7 +31,8 @@ class MrcBio(NerModel):
         self.dropout = nn.Dropout(params.get("dropout_rate", 0.2))
         self.logits = nn.Linear(cfg.hidden_size, 3)
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         seq = self.bert(features["token_ids"], features["mask"],
                         features.get("segment_ids"))
         logits = self.logits(self.dropout(seq))
@@ -40,5 +41,9 @@ class MrcBio(NerModel):
         if "label_ids" in features:
             loss = ops.masked_cross_entropy(logits, features["label_ids"],
                                             text_mask)
-        pred = logits.argmax(-1) * text_mask if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = None, None
+        if compute_pred or compute_conf:
+            pred = logits.argmax(-1) * text_mask
+        if compute_conf:
+            conf = ops.token_path_scores(logits, text_mask, pred)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)

@@ -71,7 +71,8 @@ class BertBilstmCrfMtl(NerModel):
         seq = self.bert(features["token_ids"], features["mask"])
         return self.dropout(seq)
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")
@@ -87,12 +88,26 @@ class BertBilstmCrfMtl(NerModel):
         loss = None
         if "label_ids" in features:
             loss = self._mtl_loss(features, logit0, logit1, sample_task, B)
-        pred = None
-        if compute_pred:
-            p0 = self.tower0.crf.decode(logit0, features["mask"])
-            p1 = self.tower1.crf.decode(logit1, features["mask"])
-            pred = torch.where(sample_task[:, None] == 0, p0, p1)
-        return ModelOutput(loss, pred, task_ids=task_ids)
+        pred, conf = self._decode_towers(features["mask"], logit0, logit1,
+                                         sample_task, compute_pred,
+                                         compute_conf)
+        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf)
+
+    def _decode_towers(self, mask, logit0, logit1, sample_task,
+                       compute_pred, compute_conf):
+        """Both towers decode; each sample keeps its own task's tags, and
+        with compute_conf its own task's span scores."""
+        if not (compute_pred or compute_conf):
+            return None, None
+        p0, c0 = self.tower0.crf.predict(logit0, mask, True, compute_conf)
+        p1, c1 = self.tower1.crf.predict(logit1, mask, True, compute_conf)
+        first = sample_task[:, None] == 0
+        pred = torch.where(first, p0, p1)
+        conf = None
+        if compute_conf:
+            conf = (torch.where(first, c0[0], c1[0]),
+                    torch.where(first, c0[1], c1[1]))
+        return pred, conf
 
     def _mtl_loss(self, features, logit0, logit1, sample_task, B):
         # per-task masked NLL: -ll per sample, masked by task membership
@@ -136,7 +151,8 @@ class BertBilstmCrfAdv(BertBilstmCrfMtl):
         in1 = in_dim + (2 * hidden if self.asymmetry else 0)
         self.tower1 = TaskTower(in1, hidden, self.label_sizes[1], act, keep)
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")
@@ -162,9 +178,7 @@ class BertBilstmCrfAdv(BertBilstmCrfMtl):
             task_loss = self._mtl_loss(features, logit0, logit1, sample_task, B)
             adv = nn.functional.cross_entropy(adv_logits.float(), sample_task)
             loss = task_loss + self.lam * adv
-        pred = None
-        if compute_pred:
-            p0 = self.tower0.crf.decode(logit0, features["mask"])
-            p1 = self.tower1.crf.decode(logit1, features["mask"])
-            pred = torch.where(sample_task[:, None] == 0, p0, p1)
-        return ModelOutput(loss, pred, task_ids=task_ids)
+        pred, conf = self._decode_towers(features["mask"], logit0, logit1,
+                                         sample_task, compute_pred,
+                                         compute_conf)
+        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf)

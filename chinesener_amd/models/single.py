@@ -45,7 +45,8 @@ class BilstmCrf(NerModel):
     def _enhance(self, features, emb):
         return emb
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         lens = _lens(features)
         emb = self.emb_dropout(self.embedding(features["token_ids"]))
         emb = self._enhance(features, emb)
@@ -56,8 +57,9 @@ class BilstmCrf(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred = self.crf.decode(logits, features["mask"]) if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
+                                      compute_conf)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
 
 
 class BilstmCrfSoftword(BilstmCrf):
@@ -140,13 +142,18 @@ class BertCe(BertBase):
         super().__init__(params)
         self.logits = nn.Linear(self.hidden, params["label_size"])
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         logits = self.logits(self.encode(features))
         loss = None
         if "label_ids" in features:
             loss = self._loss(logits, features)
-        pred = logits.argmax(-1) * features["mask"] if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = None, None
+        if compute_pred or compute_conf:
+            pred = logits.argmax(-1) * features["mask"]
+        if compute_conf:
+            conf = ops.token_path_scores(logits, features["mask"], pred)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
 
     def _loss(self, logits, features):
         return ops.masked_cross_entropy(logits, features["label_ids"],
@@ -176,15 +183,17 @@ class BertCrf(BertBase):
     def encode_hidden(self, features):
         return self.encode(features)
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         logits = self.logits(self.encode_hidden(features))
         loss = None
         if "label_ids" in features:
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred = self.crf.decode(logits, features["mask"]) if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
+                                      compute_conf)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
 
 
 class BertBilstmCrf(BertCrf):
@@ -238,7 +247,8 @@ class BertBilstmCrfBigram(NerModel):
         self.logits = nn.Linear(2 * self.bilstm.hidden_size, params["label_size"])
         self.crf = CRF(params["label_size"])
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         if self.use_bert:
             emb = self.encoder(features["token_ids"], features["mask"])
         else:
@@ -254,8 +264,9 @@ class BertBilstmCrfBigram(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred = self.crf.decode(logits, features["mask"]) if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
+                                      compute_conf)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
 
 
 class BertBilstmCrfSoftlexicon(BertCrf):

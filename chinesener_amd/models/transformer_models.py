@@ -34,7 +34,8 @@ class TransformerCrfBichar(NerModel):
         self.logits = nn.Linear(d_model, params["label_size"])
         self.crf = CRF(params["label_size"])
 
-    def forward(self, features, compute_pred: bool = False) -> ModelOutput:
+    def forward(self, features, compute_pred: bool = False,
+                compute_conf: bool = False) -> ModelOutput:
         emb = torch.cat([self.char_emb(features["token_ids"]),
                          self.bichar_emb(features["bichar_ids"])], dim=-1)
         x = self.project(emb)
@@ -46,8 +47,9 @@ class TransformerCrfBichar(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred = self.crf.decode(logits, features["mask"]) if compute_pred else None
-        return ModelOutput(loss, pred, logits=logits)
+        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
+                                      compute_conf)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
 
 
 class TransformerTenerCrfBichar(TransformerCrfBichar):

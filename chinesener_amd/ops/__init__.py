@@ -58,6 +58,7 @@ from .functional import (  # noqa: E402,F401
     embed3,
     layernorm, linear, linear_attention_qkv, linear_dropout_add_layernorm,
     crf_nll,
-    crf_viterbi, bilstm, softlexicon_fuse, masked_cross_entropy, dice_loss,
+    crf_viterbi, crf_path_posterior, crf_decode_scored, token_path_scores,
+    bilstm, softlexicon_fuse, masked_cross_entropy, dice_loss,
     tener_attention,
 )

@@ -722,6 +722,49 @@ def crf_viterbi(emissions, mask, transitions):
         return ref.crf_decode(emissions, mask, transitions)
 
 
+def crf_path_posterior(emissions, mask, transitions, path):
+    """(span_a, span_b), fp64 [B,L]: log P(y_s..y_e = path_s..path_e | x) =
+    span_a[s] + span_b[e] for 0 <= s <= e < len (ops.reference
+    .crf_path_posterior has the definitions). Zeros at t >= len. The score
+    is the posterior that positions s..e carry exactly these tags; under BIO
+    it does not condition on the entity ending at e, so it is an upper bound
+    on the strict-entity posterior. No autograd."""
+    with torch.no_grad():
+        if hip_enabled(emissions):
+            lens = mask.long().sum(1).to(torch.int32)
+            a, b = get_ext().crf_path_posterior(
+                emissions.detach().float().contiguous(), lens,
+                transitions.detach().float().contiguous(),
+                path.to(torch.int32).contiguous())
+            return a, b
+        return ref.crf_path_posterior(emissions, mask, transitions, path)
+
+
+def crf_decode_scored(emissions, mask, transitions):
+    """Viterbi decode plus the posterior arrays of the decoded path:
+    (pred [B,L], span_a, span_b). pred is exactly crf_viterbi's."""
+    pred = crf_viterbi(emissions, mask, transitions)
+    span_a, span_b = crf_path_posterior(emissions, mask, transitions, pred)
+    return pred, span_a, span_b
+
+
+def token_path_scores(logits, mask, pred):
+    """The span_a/span_b pair for heads that score tokens independently
+    (softmax heads): with cum the running sum of log p_t(pred_t) over the
+    masked tokens, span_a[t] = -cum_{<t} and span_b[t] = cum_{<=t}, so
+    span_a[s] + span_b[e] is the log of the product of the token
+    probabilities over s..e. fp64, zeros outside the mask, no autograd."""
+    with torch.no_grad():
+        m = mask.to(torch.bool)
+        lp = torch.log_softmax(logits.detach().double(), dim=-1)
+        lp = lp.gather(2, pred.long()[:, :, None]).squeeze(2)
+        lp = torch.where(m, lp, torch.zeros_like(lp))
+        cum = torch.cumsum(lp, dim=1)
+        zeros = torch.zeros_like(cum)
+        return (torch.where(m, lp - cum, zeros),
+                torch.where(m, cum, zeros))
+
+
 # ----------------------------------------------------------------- lstm
 class _LstmDirFn(torch.autograd.Function):
     @staticmethod

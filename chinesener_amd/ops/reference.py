@@ -282,6 +282,66 @@ def crf_decode(emissions: torch.Tensor, mask: torch.Tensor,
     return out * (pos < lens[:, None]).long()
 
 
+def crf_path_posterior(emissions: torch.Tensor, mask: torch.Tensor,
+                       transitions: torch.Tensor, path: torch.Tensor,
+                       dtype: torch.dtype = torch.float64
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Log-posterior of a tag path under the CRF, as two [B,L] arrays:
+
+        log P(y_s..y_e = path_s..path_e | x) = span_a[s] + span_b[e]
+
+    for every 0 <= s <= e < len, with
+
+        span_a[t] = alpha_t(p_t) - C_t           (>= 0)
+        span_b[t] = beta_t(p_t) + C_t - logZ     (<= 0)
+
+    where alpha/beta are the log forward/backward messages and C_t the score
+    of the path prefix 0..t. s == e is the token marginal of the path tag;
+    s = 0, e = len-1 the sequence probability. Cells at t >= len, and rows
+    with len == 0, hold 0; path ids are clamped to [0, T-1].
+
+    The score says that positions s..e carry exactly these tags. Under BIO
+    it does not also say that the entity stops at e, so it is an upper bound
+    on the posterior of the strict entity.
+
+    Plain recurrences in ``dtype`` (no running offsets): the ground truth
+    for the HIP kernel."""
+    B, L, T = emissions.shape
+    em = emissions.detach().to(dtype)
+    tr = transitions.detach().to(dtype)
+    lens = mask.long().sum(1)                                    # [B]
+    p = path.long().clamp(0, T - 1)
+    pos = torch.arange(L, device=em.device)
+    valid = pos[None, :] < lens[:, None]                         # [B,L]
+    alphas = [em[:, 0]]
+    for t in range(1, L):
+        alphas.append(torch.logsumexp(
+            alphas[-1][:, :, None] + tr[None, :, :], dim=1) + em[:, t])
+    alphas = torch.stack(alphas, dim=1)                          # [B,L,T]
+    zero = torch.zeros(B, T, dtype=dtype, device=em.device)
+    betas = [zero] * L                     # beta_t = 0 for every t >= len-1
+    beta = zero
+    for t in range(L - 2, -1, -1):
+        nxt = torch.logsumexp(
+            tr[None, :, :] + (em[:, t + 1] + beta)[:, None, :], dim=2)
+        beta = torch.where(((t + 1) < lens)[:, None], nxt, zero)
+        betas[t] = beta
+    betas = torch.stack(betas, dim=1)                            # [B,L,T]
+    last = (lens - 1).clamp(min=0)
+    log_z = torch.logsumexp(
+        alphas[torch.arange(B, device=em.device), last], dim=1)  # [B]
+    x_p = em.gather(2, p[:, :, None]).squeeze(2)                 # [B,L]
+    inc = x_p.clone()
+    inc[:, 1:] = inc[:, 1:] + tr[p[:, :-1], p[:, 1:]]
+    c = torch.cumsum(inc * valid.to(dtype), dim=1)               # C_t
+    a_p = alphas.gather(2, p[:, :, None]).squeeze(2)
+    b_p = betas.gather(2, p[:, :, None]).squeeze(2)
+    zeros = torch.zeros_like(c)
+    span_a = torch.where(valid, a_p - c, zeros)
+    span_b = torch.where(valid, b_p + c - log_z[:, None], zeros)
+    return span_a, span_b
+
+
 # ------------------------------------------------------------------ lstm
 def lstm_forward(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
                  b: torch.Tensor, lens: torch.Tensor, reverse: bool = False,

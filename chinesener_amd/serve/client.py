@@ -70,8 +70,10 @@ class PredictionClient:
 
     @grpc_retry
     def predict(self, model_name: str, inputs: Dict[str, np.ndarray],
-                version: Optional[int] = None) -> Dict:
-        req = rpc.dumps(rpc.make_predict_request(model_name, inputs, version))
+                version: Optional[int] = None,
+                options: Optional[Dict] = None) -> Dict:
+        req = rpc.dumps(rpc.make_predict_request(model_name, inputs, version,
+                                                 options=options))
         raw = self._call(req, timeout=self.timeout_s)
         return rpc.loads(raw)
 

@@ -11,13 +11,18 @@ replays one pre-built graph: zero launch latency for ~100 small kernels.
 Batch shapes are fixed at capture time; warmup requests (warmup.py,
 mirroring the reference's TF-Serving warmup records) establish them.
 Requests are padded up to the nearest captured batch size.
+
+With ``confidence=True`` the same path also runs the CRF path-posterior
+kernel (token-softmax heads: a cumulative log-softmax) and the captured
+outputs are (pred_ids, span_a, span_b): log P(tokens s..e carry the
+decoded tags) = span_a[s] + span_b[e], see ops.crf_path_posterior.
 """
 from __future__ import annotations
 
 import logging
 import threading
 import time
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -43,7 +48,7 @@ _DEFAULTABLE_KEYS = frozenset({
 
 class _CapturedGraph:
     def __init__(self, graph, static_in: Dict[str, torch.Tensor],
-                 static_out: torch.Tensor):
+                 static_out: Tuple[torch.Tensor, ...]):
         self.graph = graph
         self.static_in = static_in
         self.static_out = static_out
@@ -58,8 +63,10 @@ class InferenceEngine:
                  batch_sizes: Sequence[int] = (1, 4, 8),
                  max_seq_len: Optional[int] = None,
                  use_graph: Optional[bool] = None,
-                 device: Optional[str] = None):
+                 device: Optional[str] = None,
+                 confidence: bool = False):
         self.name = name
+        self.confidence = bool(confidence)
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         self.model, self.params = load_exported(name, export_root,
                                                 device=self.device,
@@ -110,6 +117,15 @@ class InferenceEngine:
             out[k] = v.to(self.device)
         return out
 
+    def _forward(self, feats: Dict[str, torch.Tensor]
+                 ) -> Tuple[torch.Tensor, ...]:
+        """(pred_ids,) or, on a confidence engine, (pred_ids, span_a,
+        span_b)."""
+        if not self.confidence:
+            return (self.model(feats, compute_pred=True).pred_ids,)
+        out = self.model(feats, compute_pred=True, compute_conf=True)
+        return (out.pred_ids,) + tuple(out.span_scores)
+
     @torch.no_grad()
     def _capture(self, batch: int) -> _CapturedGraph:
         static_in = self._example_features(batch)
@@ -118,12 +134,11 @@ class InferenceEngine:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                out = self.model(static_in, compute_pred=True)
+                self._forward(static_in)
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self.model(static_in, compute_pred=True)
-            static_out = out.pred_ids
+            static_out = self._forward(static_in)
         log.info("hipGraph captured for %s batch=%d L=%d", self.name, batch,
                  self.max_seq_len)
         return _CapturedGraph(graph, static_in, static_out)
@@ -160,9 +175,28 @@ class InferenceEngine:
         hipGraph static input/output buffers are shared state — without
         the lock two in-flight requests would overwrite each other."""
         with self._lock:
-            return self._predict(features)
+            return self._predict(features)[0]
 
-    def _predict(self, features: Dict[str, np.ndarray]) -> np.ndarray:
+    @torch.no_grad()
+    def predict_scored(self, features: Dict[str, np.ndarray]
+                       ) -> Dict[str, np.ndarray]:
+        """predict() plus the span scores of the decoded tags:
+        {"pred_ids" [B,L], "span_a" [B,L] f64, "span_b" [B,L] f64}. For
+        tokens s..e of a row, exp(span_a[s] + span_b[e]) is the posterior
+        that they carry exactly the decoded tags (an upper bound on the
+        strict BIO entity's, which would also need the entity to stop at
+        e); eval.decode_prediction_scored turns it into per-entity
+        confidences. Needs an engine built with confidence=True."""
+        if not self.confidence:
+            raise RuntimeError(
+                f"engine for '{self.name}' was built without confidence=True;"
+                " predict_scored needs InferenceEngine(..., confidence=True)")
+        with self._lock:
+            pred, span_a, span_b = self._predict(features)
+        return {"pred_ids": pred, "span_a": span_a, "span_b": span_b}
+
+    def _predict(self, features: Dict[str, np.ndarray]
+                 ) -> Tuple[np.ndarray, ...]:
         self.n_requests += 1
         batch = features["token_ids"].shape[0]
         tensors = {}
@@ -199,12 +233,11 @@ class InferenceEngine:
                 buf[tuple(sl)].copy_(t.to(self.device), non_blocking=True)
             g.graph.replay()
             torch.cuda.synchronize()
-            return g.static_out[:batch].cpu().numpy()
+            return tuple(o[:batch].cpu().numpy() for o in g.static_out)
 
         # eager path (CPU, or batch larger than any bucket)
         dev = {k: t.to(self.device) for k, t in tensors.items()}
-        out = self.model(dev, compute_pred=True)
-        return out.pred_ids.cpu().numpy()
+        return tuple(o.cpu().numpy() for o in self._forward(dev))
 
 
 class MicroBatcher:
@@ -234,6 +267,10 @@ class MicroBatcher:
     def name(self):
         return self.engine.name
 
+    @property
+    def confidence(self):
+        return self.engine.confidence
+
     def warmup(self, requests=None):
         return self.engine.warmup(requests)
 
@@ -244,8 +281,22 @@ class MicroBatcher:
         self._worker.join(timeout=2.0)
 
     def predict(self, features: Dict[str, np.ndarray]) -> np.ndarray:
+        return self._submit(features, scored=False)
+
+    def predict_scored(self, features: Dict[str, np.ndarray]
+                       ) -> Dict[str, np.ndarray]:
+        """Engine.predict_scored through the batcher. Scored and plain
+        requests of one signature share a replay; each caller gets back
+        what it asked for."""
+        if not self.engine.confidence:
+            raise RuntimeError(
+                f"engine for '{self.name}' was built without confidence=True;"
+                " predict_scored needs InferenceEngine(..., confidence=True)")
+        return self._submit(features, scored=True)
+
+    def _submit(self, features: Dict[str, np.ndarray], scored: bool):
         ev = threading.Event()
-        slot: Dict[str, object] = {}
+        slot: Dict[str, object] = {"scored": scored}
         with self._cv:
             self._queue.append((features, slot, ev))
             self._cv.notify()
@@ -312,11 +363,17 @@ class MicroBatcher:
                 merged = {k: np.concatenate(
                     [np.asarray(f[k]) for f, _, _ in batch])
                     for k in batch[0][0]}
-                out = self.engine.predict(merged)
+                if any(slot["scored"] for _, slot, _ in batch):
+                    full = self.engine.predict_scored(merged)
+                else:
+                    full = {"pred_ids": self.engine.predict(merged)}
                 i = 0
                 for f, slot, ev in batch:
                     n = int(np.asarray(f["token_ids"]).shape[0])
-                    slot["out"] = out[i:i + n]
+                    if slot["scored"]:
+                        slot["out"] = {k: v[i:i + n] for k, v in full.items()}
+                    else:
+                        slot["out"] = full["pred_ids"][i:i + n]
                     i += n
             except Exception as e:
                 for _, slot, ev in batch:
@@ -337,3 +394,6 @@ class FastPredict:
 
     def predict(self, features):
         return self.engine.predict(features)
+
+    def predict_scored(self, features):
+        return self.engine.predict_scored(features)

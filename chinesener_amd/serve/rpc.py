@@ -53,7 +53,14 @@ def loads(raw: bytes) -> Dict:
 
 def make_predict_request(model_name: str, inputs: Dict[str, np.ndarray],
                          version: int | None = None,
-                         signature: str = "serving_default") -> Dict:
-    return {"model_spec": {"name": model_name, "version": version,
-                           "signature_name": signature},
-            "inputs": inputs}
+                         signature: str = "serving_default",
+                         options: Dict[str, Any] | None = None) -> Dict:
+    """``options={"confidence": True}`` asks for span_a/span_b next to
+    pred_ids in the response's outputs (the server must run with
+    confidence enabled). Without options the request is unchanged."""
+    req = {"model_spec": {"name": model_name, "version": version,
+                          "signature_name": signature},
+           "inputs": inputs}
+    if options:
+        req["options"] = dict(options)
+    return req

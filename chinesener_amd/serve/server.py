@@ -50,11 +50,19 @@ class PredictionServicer:
             context.abort(grpc.StatusCode.NOT_FOUND,
                           f"model '{name}' not loaded "
                           f"(loaded: {sorted(self.engines)})")
+        scored = bool((req.get("options") or {}).get("confidence"))
+        if scored and not engine.confidence:
+            context.abort(grpc.StatusCode.FAILED_PRECONDITION,
+                          f"model '{name}' is served without confidence; "
+                          "start the server with --confidence")
         try:
             t0 = time.perf_counter()
-            pred = engine.predict(req["inputs"])
+            if scored:
+                outputs = engine.predict_scored(req["inputs"])
+            else:
+                outputs = {"pred_ids": engine.predict(req["inputs"])}
             ms = (time.perf_counter() - t0) * 1000
-            return rpc.dumps({"outputs": {"pred_ids": pred},
+            return rpc.dumps({"outputs": outputs,
                               "model_spec": req["model_spec"],
                               "latency_ms": ms})
         except Exception as e:  # surface as INTERNAL with the message
@@ -79,11 +87,12 @@ def build_server(engines: Dict[str, InferenceEngine], port: int,
 def serve(model_names, export_root: str = EXPORT_DIR,
           port: int = rpc.DEFAULT_PORT, wait: bool = True,
           use_graph=None, batch_sizes=(1, 4, 8), max_workers: int = 4,
-          batching: bool = True, window_ms: float = 0.3):
+          batching: bool = True, window_ms: float = 0.3,
+          confidence: bool = False):
     engines = {}
     for name in model_names:
         eng = InferenceEngine(name, export_root, batch_sizes=batch_sizes,
-                              use_graph=use_graph)
+                              use_graph=use_graph, confidence=confidence)
         warm = load_warmup(latest_version_dir(name, export_root))
         eng.warmup(warm)
         log.info("loaded %s (%d warmup requests replayed)", name, len(warm))
@@ -108,11 +117,14 @@ def main(argv=None):
                     help="disable hipGraph capture (debug)")
     ap.add_argument("--no_batching", action="store_true",
                     help="disable concurrent-request micro-batching")
+    ap.add_argument("--confidence", action="store_true",
+                    help="also compute span scores, for requests that ask "
+                         "for entity confidences")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     serve(args.model.split(","), args.export_root, args.port,
           use_graph=False if args.no_graph else None,
-          batching=not args.no_batching)
+          batching=not args.no_batching, confidence=args.confidence)
     return 0
 
 

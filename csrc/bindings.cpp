@@ -54,6 +54,12 @@ std::vector<at::Tensor> crf_wide_fwd(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, const at::Tensor&);
 at::Tensor crf_wide_viterbi(const at::Tensor&, const at::Tensor&,
                             const at::Tensor&);
+// crf_posterior.hip (T <= 64, L <= 512): log-posterior of a given tag path,
+// as two fp64 [B,L] arrays {span_a, span_b}
+std::vector<at::Tensor> crf_path_posterior(const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&,
+                                           const at::Tensor&);
 // softlexicon.hip
 at::Tensor softlexicon_fwd(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&);
@@ -177,6 +183,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("embed3_fwd", &embed3_fwd);
   m.def("crf_fwd", &crf_fwd);
   m.def("crf_viterbi", &crf_viterbi);
+  m.def("crf_path_posterior", &crf_path_posterior, py::arg("emissions"),
+        py::arg("lens"), py::arg("transitions"), py::arg("path"));
   m.def("softlexicon_fwd", &softlexicon_fwd);
   m.def("softlexicon_bwd", &softlexicon_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);

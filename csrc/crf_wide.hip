@@ -17,23 +17,17 @@
 // the offsets cancel term by term in the marginals and never appear in
 // them; only logZ adds them up, in fp64. Without this alpha reaches ~2.7e3
 // at L=512, T=64 and its fp32 ulp (2.4e-4 per step) shows in the grads.
-#include "common.h"
-
-#define NEG (-1e30f)
+#include "crf_common.h"
 
 namespace {
 
-constexpr int CRFW_MAX_T = 64;
-constexpr int CRFW_MAX_L = 512;
 constexpr size_t CRFW_LDS_BYTES = 160 * 1024;
-
-inline __host__ __device__ int round4(int x) { return (x + 3) & ~3; }
 
 // ---- LDS carve, shared by host and device so the byte count lives in
 // one place. All offsets are multiples of 4 floats (16 B).
 template <int W> struct CrfWideCarve {
-  static constexpr int TRS = W + 1;                    // padded row stride
-  static constexpr int TR_FLOATS = (W * TRS + 3) & ~3; // transition image
+  static constexpr int TRS = CrfTransImage<W>::TRS;
+  static constexpr int TR_FLOATS = CrfTransImage<W>::TR_FLOATS;
   // fwd, per wave: alpha [L][TP] (reused as the [T][TRS] dtrans tile once
   // the backward scan is done), cur [W], k [LP], tags [LP]
   static __host__ __device__ int alpha_floats(int L, int T) {
@@ -55,17 +49,6 @@ template <int W> struct CrfWideCarve {
     return sizeof(float) * (size_t)TR_FLOATS + (size_t)nw * vit_wave_bytes(L);
   }
 };
-
-template <int W>
-__device__ __forceinline__ void stage_trans(float* tr_s,
-                                            const float* __restrict__ trans,
-                                            int T) {
-  constexpr int TRS = CrfWideCarve<W>::TRS;
-  for (int idx = threadIdx.x; idx < W * TRS; idx += blockDim.x) {
-    const int i = idx / TRS, j = idx - i * TRS;
-    tr_s[idx] = (i < T && j < T) ? trans[i * T + j] : NEG;
-  }
-}
 
 // ------------------------------------------------------------------ fwd
 template <int W>
@@ -106,8 +89,7 @@ __global__ __launch_bounds__(256) void crf_wide_fwd_kernel(
 
   // this lane's column of the transitions, held for the forward scan
   float trc[W];
-#pragma unroll
-  for (int i = 0; i < W; ++i) trc[i] = tr_s[i * TRS + jc];
+  load_trans_col<W>(tr_s, jc, trc);
   for (int t = lane; t < n; t += WAVE) tg_s[t] = min(max(tg[t], 0), T - 1);
 
   // ---- forward scan: alpha_hat[t][:] in LDS, pad cells [T,TP) = NEG ----
@@ -119,13 +101,13 @@ __global__ __launch_bounds__(256) void crf_wide_fwd_kernel(
     const float et = e_nxt;
     if (act && t + 1 < n) e_nxt = e[(t + 1) * T + j];
     __builtin_amdgcn_wave_barrier();
-    const f32x4* ap = reinterpret_cast<const f32x4*>(alpha + (t - 1) * TP);
+    const float* ap = alpha + (t - 1) * TP;
     float v[W];
     f32x4 m4 = {NEG, NEG, NEG, NEG}, k4 = {NEG, NEG, NEG, NEG};
 #pragma unroll
     for (int q = 0; q < W / 4; ++q) {
       if (q * 4 < T) {
-        const f32x4 a4 = ap[q];  // same address in every lane: broadcast
+        const f32x4 a4 = lds_bcast4(ap, q);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           v[q * 4 + c] = a4[c] + trc[q * 4 + c];
@@ -176,11 +158,9 @@ __global__ __launch_bounds__(256) void crf_wide_fwd_kernel(
   }
   float trr[W];      // this lane's row of the transitions
   float exp_row[W];  // lane i: sum_t P(y_t=i, y_{t+1}=jj)
+  load_trans_row<W>(tr_s, jc, trr);
 #pragma unroll
-  for (int q = 0; q < W; ++q) {
-    trr[q] = tr_s[jc * TRS + q];
-    exp_row[q] = 0.f;
-  }
+  for (int q = 0; q < W; ++q) exp_row[q] = 0.f;
   e_nxt = act ? e[(n - 1) * T + j] : 0.f;
   for (int t = n - 2; t >= 0; --t) {
     // cur[jj] = e[t+1][jj] + beta_hat[t+1][jj], staged for a broadcast read
@@ -191,13 +171,12 @@ __global__ __launch_bounds__(256) void crf_wide_fwd_kernel(
     __builtin_amdgcn_wave_barrier();
     const float k = k_s[t + 1];
     const float a_ti = alpha[t * TP + jc];  // lane = i here
-    const f32x4* cp = reinterpret_cast<const f32x4*>(cur_s);
     float row[W];  // trans[i=lane][jj] + cur[jj], then exp(. - m)
     f32x4 m4 = {NEG, NEG, NEG, NEG};
 #pragma unroll
     for (int q = 0; q < W / 4; ++q) {
       if (q * 4 < T) {
-        const f32x4 c4 = cp[q];
+        const f32x4 c4 = lds_bcast4(cur_s, q);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           row[q * 4 + c] = trr[q * 4 + c] + c4[c];
@@ -284,8 +263,7 @@ __global__ __launch_bounds__(256) void crf_wide_viterbi_kernel(
   const bool act = j < T;
   const int jc = lane & (W - 1);
   float trc[W];
-#pragma unroll
-  for (int i = 0; i < W; ++i) trc[i] = tr_s[i * TRS + jc];
+  load_trans_col<W>(tr_s, jc, trc);
 
   float delta = act ? e[j] : NEG;  // delta[0][j]
   float e_nxt = (act && n > 1) ? e[T + j] : 0.f;
@@ -295,7 +273,6 @@ __global__ __launch_bounds__(256) void crf_wide_viterbi_kernel(
     __builtin_amdgcn_wave_barrier();
     if (lane < W) dl_s[lane] = delta;
     __builtin_amdgcn_wave_barrier();
-    const f32x4* dp = reinterpret_cast<const f32x4*>(dl_s);
     // four contiguous index blocks scanned independently, then merged in
     // index order with a strict '>' so the first maximum wins
     float best[4];
@@ -307,7 +284,7 @@ __global__ __launch_bounds__(256) void crf_wide_viterbi_kernel(
 #pragma unroll
       for (int q = h * (W / 16); q < (h + 1) * (W / 16); ++q) {
         if (q * 4 < T) {
-          const f32x4 d4 = dp[q];
+          const f32x4 d4 = lds_bcast4(dl_s, q);
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const float v = d4[c] + trc[q * 4 + c];
@@ -355,13 +332,6 @@ __global__ __launch_bounds__(256) void crf_wide_viterbi_kernel(
       pr[t] = cur;
     }
   }
-}
-
-void check_wide_range(int L, int T) {
-  TORCH_CHECK(T >= 1 && T <= CRFW_MAX_T && L >= 1 && L <= CRFW_MAX_L,
-              "CRF: label_size ", T, " / seq_len ", L,
-              " outside the supported range (1 <= label_size <= ", CRFW_MAX_T,
-              ", 1 <= seq_len <= ", CRFW_MAX_L, ")");
 }
 
 // waves per block: the most of 4, 2, 1 whose LDS fits

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from chinesener_amd.data.datasets import get_spec
 from chinesener_amd.data.preprocess import extract_prefix_surfix, get_instance
-from chinesener_amd.eval import extract_entity
+from chinesener_amd.eval import decode_prediction_scored, extract_entity
 from chinesener_amd.serve.client import PredictionClient, timer
 from chinesener_amd.serve import rpc
 
@@ -61,6 +61,23 @@ class InferHelper:
                 for i in pred_ids[offset:offset + len(tokens)]]
         return extract_entity(tokens, tags)
 
+    @timer
+    def infer_scored(self, sentence: str):
+        """infer()'s entities in order of appearance, each as {"type",
+        "text", "start", "end", "confidence"}; the server must run with
+        --confidence. The confidence is the model's posterior that the
+        span's tokens carry exactly the decoded tags."""
+        feats = self.make_feature(sentence)
+        resp = self.client.predict(self.model_name, feats, self.version,
+                                   options={"confidence": True})
+        out = resp["outputs"]
+        tokens = self.proc.tokenizer.tokenize(sentence)
+        offset = 1 if self.proc.is_bert else 0  # skip [CLS]
+        tags = [self.idx2tag.get(int(i), "O")
+                for i in out["pred_ids"][0][offset:offset + len(tokens)]]
+        return decode_prediction_scored(tokens, tags, out["span_a"][0],
+                                        out["span_b"][0], offset=offset)
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
@@ -70,11 +87,15 @@ def main(argv=None):
     ap.add_argument("--port", type=int, default=rpc.DEFAULT_PORT)
     ap.add_argument("--text", default=None,
                     help="one-shot inference instead of the REPL")
+    ap.add_argument("--confidence", action="store_true",
+                    help="print each entity with its confidence (server "
+                         "started with --confidence)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     helper = InferHelper(args.model, args.data, args.host, args.port)
+    infer = helper.infer_scored if args.confidence else helper.infer
     if args.text:
-        print(helper.infer(args.text))
+        print(infer(args.text))
         return 0
     while True:  # reference inference.py:110-115 interactive loop
         try:
@@ -83,7 +104,7 @@ def main(argv=None):
             break
         if not text or text in ("q", "quit", "exit"):
             break
-        print(helper.infer(text))
+        print(infer(text))
     return 0
 
 

@@ -1,13 +1,19 @@
-"""CRF kernel timing: crf_fwd (loss + grads in one pass) and crf_viterbi at
-B=64 over the tag counts either side of the narrow/wide boundary, next to
+"""CRF kernel timing: crf_fwd (loss + grads in one pass), crf_viterbi and
+crf_path_posterior at B=64 over the tag counts either side of the
+narrow/wide boundary and at the serving shapes (B = 1, 8), next to
 ops.reference (fwd+bwd / decode) on the same GPU and the same inputs.
-Correctness is covered by tests/test_gpu_kernels.py and
-tests/test_gpu_crf_wide.py; this times the extension entry points only.
+crf_fwd and crf_path_posterior both get the Viterbi path as their tags:
+crf_fwd runs the same two scans plus the alpha table and both gradients, so
+it is the yardstick the posterior kernel must not exceed.
+Correctness is covered by tests/test_gpu_kernels.py,
+tests/test_gpu_crf_wide.py and tests/test_gpu_crf_posterior.py; this times
+the extension entry points only.
 
 Method: device events around N back-to-back calls, after warm-up; R such
 windows per shape; the table reports the median window and the min..max
-spread, in microseconds per call. A shape the extension refuses prints n/a,
-so the same script runs on a commit without the wide kernels.
+spread, in microseconds per call. A shape the extension refuses, or an op
+it does not have, prints n/a, so the same script runs on a commit without
+the wide kernels or without crf_path_posterior.
 
     python scripts/bench_crf.py [--out table.md] [--no-ref]
 """
@@ -23,7 +29,9 @@ from chinesener_amd import ops  # noqa: E402
 from chinesener_amd.ops import reference as ref  # noqa: E402
 
 SHAPES = [(64, 128, 10), (64, 128, 20), (64, 128, 24), (64, 128, 41),
-          (64, 128, 64), (64, 512, 24), (64, 512, 64)]
+          (64, 128, 64), (64, 512, 24), (64, 512, 64),
+          # serving: one request and one full bucket
+          (1, 150, 10), (8, 150, 10), (1, 128, 24), (8, 128, 24)]
 
 
 def windows(fn, n, reps, warmup):
@@ -70,7 +78,8 @@ def main():
     torch.manual_seed(0)
 
     lines = ["| B | L | T | crf_fwd us | ref fwd+bwd us | crf_viterbi us | "
-             "ref decode us |", "|---|---|---|---|---|---|---|"]
+             "ref decode us | crf_path_posterior us |",
+             "|---|---|---|---|---|---|---|---|"]
     print(torch.cuda.get_device_name(0), flush=True)
     for B, L, T in SHAPES:
         em = torch.randn(B, L, T, device="cuda")
@@ -79,12 +88,22 @@ def main():
         mask = torch.ones(B, L, dtype=torch.long, device="cuda")
         tags = torch.randint(0, T, (B, L), device="cuda")
         tags32 = tags.to(torch.int32)
-        n = 50 if L <= 128 else 20
+        n = 50 if L <= 150 else 20
+        try:  # the decoded path, where this build can decode the shape
+            tags32 = ext.crf_viterbi(em, lens, trans)
+            tags = tags32.long()
+        except RuntimeError:
+            pass
 
         fwd = try_windows(lambda: ext.crf_fwd(em, tags32, lens, trans),
                           n, args.reps, 5)
         vit = try_windows(lambda: ext.crf_viterbi(em, lens, trans),
                           n, args.reps, 5)
+        post = None
+        if hasattr(ext, "crf_path_posterior"):
+            post = try_windows(
+                lambda: ext.crf_path_posterior(em, lens, trans, tags32),
+                n, args.reps, 5)
         rfwd = rvit = None
         if not args.no_ref:
             em_g = em.clone().requires_grad_()
@@ -103,7 +122,7 @@ def main():
             rfwd = windows(ref_step, 2, 3, 1)
             rvit = windows(ref_dec, 2, 3, 1)
         row = (f"| {B} | {L} | {T} | {fmt(fwd)} | {fmt(rfwd)} | {fmt(vit)} | "
-               f"{fmt(rvit)} |")
+               f"{fmt(rvit)} | {fmt(post)} |")
         print(row, flush=True)
         lines.append(row)
     if args.out:

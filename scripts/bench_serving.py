@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Serving latency bench: hipGraph-captured BERT-BiLSTM-CRF inference
 (BASELINE.json L6 path) vs eager, batch=1 and batch=8, p50/p99 over N
-requests. Run on an MI355X box; prints one JSON line."""
+requests. Run on an MI355X box; prints one JSON line.
+
+--confidence builds the engines with confidence=True and times
+predict_scored; the difference to a run without it is what entity
+confidences cost a request. --no_concurrency skips the 8-client part."""
 from __future__ import annotations
 
 import argparse
@@ -21,6 +25,8 @@ def main():
     ap.add_argument("--requests", type=int, default=200)
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--seq_len", type=int, default=150)
+    ap.add_argument("--confidence", action="store_true")
+    ap.add_argument("--no_concurrency", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available()
 
@@ -42,22 +48,29 @@ def main():
     model = build_model(name, params)
     export_model(model, name, params, export_root="/tmp/serving_bench")
 
+    conf_kw = {"confidence": True} if args.confidence else {}
+
+    def call_of(target):
+        return target.predict_scored if args.confidence else target.predict
+
     results = {}
     for graph in (True, False):
         eng = InferenceEngine(name, "/tmp/serving_bench", batch_sizes=(1, 8),
-                              max_seq_len=args.seq_len, use_graph=graph)
+                              max_seq_len=args.seq_len, use_graph=graph,
+                              **conf_kw)
         eng.warmup()
         rng = np.random.default_rng(0)
         for batch in (1, 8):
             feats = {"token_ids": rng.integers(1, 21128, (batch, args.seq_len)),
                      "segment_ids": np.zeros((batch, args.seq_len), np.int64),
                      "mask": np.ones((batch, args.seq_len), np.int64)}
+            predict = call_of(eng)
             for _ in range(20):
-                eng.predict(feats)
+                predict(feats)
             lat = []
             for _ in range(args.requests):
                 t0 = time.perf_counter()
-                eng.predict(feats)
+                predict(feats)
                 lat.append((time.perf_counter() - t0) * 1000)
             lat.sort()
             key = f"{'graph' if graph else 'eager'}_b{batch}"
@@ -76,13 +89,15 @@ def main():
     feats1 = {"token_ids": rng.integers(1, 21128, (1, args.seq_len)),
               "segment_ids": np.zeros((1, args.seq_len), np.int64),
               "mask": np.ones((1, args.seq_len), np.int64)}
-    for mode in ("locked", "microbatch"):
+    for mode in () if args.no_concurrency else ("locked", "microbatch"):
         eng = InferenceEngine(name, "/tmp/serving_bench", batch_sizes=(1, 8),
-                              max_seq_len=args.seq_len, use_graph=True)
+                              max_seq_len=args.seq_len, use_graph=True,
+                              **conf_kw)
         eng.warmup()
         target = MicroBatcher(eng, window_ms=0.3) if mode == "microbatch" else eng
+        predict1 = call_of(target)
         for _ in range(20):
-            target.predict(feats1)
+            predict1(feats1)
         lat_all = []
         lock = threading.Lock()
         n_clients, per_client = 8, max(25, args.requests // 8)
@@ -91,7 +106,7 @@ def main():
             mine = []
             for _ in range(per_client):
                 t0 = time.perf_counter()
-                target.predict(feats1)
+                predict1(feats1)
                 mine.append((time.perf_counter() - t0) * 1000)
             with lock:
                 lat_all.extend(mine)
@@ -116,6 +131,7 @@ def main():
     print(json.dumps({
         "metric": "serving latency, bert_bilstm_crf PREDICT (BERT-12L + BiLSTM + Viterbi)",
         "seq_len": args.seq_len, "requests": args.requests,
+        "confidence": args.confidence,
         "results": results,
         "speedup_b1": round(results["eager_b1"]["p50_ms"]
                             / results["graph_b1"]["p50_ms"], 2)}))
