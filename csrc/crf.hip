@@ -28,7 +28,10 @@ __global__ void crf_fwd_kernel(const float* __restrict__ emis,  // [B,L,T]
   const int b = blockIdx.x * nw + wid;
   if (b >= B) return;
   const int n = lens[b];
-  if (n <= 0) return;
+  if (n <= 0) {  // empty row: ll is 0, demis/dtrans stay zero
+    if (lane == 0) ll[b] = 0.f;
+    return;
+  }
   const float* e = emis + (long)b * L * T;
   const int* tg = tags + (long)b * L;
   float* alpha = alpha_all + (long)wid * L * T;
@@ -36,39 +39,57 @@ __global__ void crf_fwd_kernel(const float* __restrict__ emis,  // [B,L,T]
   const bool act = j < T;
 
   // ---- forward pass: alpha[t][:] in LDS ----
+  // Stored relative to a running offset: LDS holds alpha[t][j] - C(t),
+  // C(t) = C(t-1) + stored alpha[t-1][0]. The stored values stay within
+  // one step's spread however long the row is, so exp(alpha + beta - logZ)
+  // below does not lose ulp(|alpha|), which grows with t.
   if (act) alpha[j] = e[j];
   for (int t = 1; t < n; ++t) {
     float m = NEG;
     if (act) {
+      const float ea = e[t * T + j] - alpha[(t - 1) * T];
       for (int i = 0; i < T; ++i)
         m = fmaxf(m, alpha[(t - 1) * T + i] + tr_s[i * T + j]);
       float s = 0.f;
       for (int i = 0; i < T; ++i)
         s += __expf(alpha[(t - 1) * T + i] + tr_s[i * T + j] - m);
-      alpha[t * T + j] = m + __logf(s) + e[t * T + j];
+      alpha[t * T + j] = m + __logf(s) + ea;
     }
   }
-  // logZ = lse over lanes j < T of alpha[n-1]
+  // logZ = C(n-1) + lz, lz = lse over lanes j < T of the stored alpha[n-1]
   float av = act ? alpha[(n - 1) * T + j] : NEG;
   const float mz = wave_reduce_max(av);
   const float sz = wave_reduce_sum(act ? __expf(av - mz) : 0.f);
-  const float logZ = mz + __logf(sz);
+  const float lz = mz + __logf(sz);
 
-  // ---- gold score (lane 0, serial — n steps of scalar work) ----
-  if (lane == 0) {
-    float sc = e[tg[0]];
-    for (int t = 1; t < n; ++t)
+  // ---- gold score: the wave's lanes stride over t ----
+  // the same loop sums C(n-1) in fp64: only ll needs it
+  {
+    float sc = 0.f;
+    double c_off = 0.0;
+    for (int t = 1 + lane; t < n; t += WAVE) {
       sc += tr_s[tg[t - 1] * T + tg[t]] + e[t * T + tg[t]];
-    ll[b] = sc - logZ;
+      c_off += (double)alpha[(t - 1) * T];
+    }
+    sc = wave_reduce_sum(sc);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c_off += __shfl_xor(c_off, off);
+    if (lane == 0)
+      ll[b] = (float)((double)(e[tg[0]] + sc) - (c_off + (double)lz));
   }
 
   // ---- backward pass + grads ----
-  // beta held in registers per lane; expected transition counts
-  // accumulated per lane i over its row.
+  // beta held in registers per lane, relative to D(t+1) + cur[0] of its
+  // step; expected transition counts accumulated per lane i over its row.
+  // kd = C(t) + D(t+1) - logZ is what the stored alpha[t] and this step's
+  // row lack of alpha + trans + e + beta - logZ. It starts at -lz and moves
+  // by one step's offsets in fp64, so it stays small and exact.
   float* de = demis + (long)b * L * T;
   float beta = 0.f;  // beta[n-1][j] = 0
+  double kd = -(double)lz;
+  float p_prev = 0.f;
   if (act) {
-    const float marg = __expf(alpha[(n - 1) * T + j] + beta - logZ);
+    const float marg = __expf(alpha[(n - 1) * T + j] + beta - lz);
     de[(n - 1) * T + j] = ((j == tg[n - 1]) ? 1.f : 0.f) - marg;
   }
   float exp_row[TMAX];  // lane i: sum_t P(y_t=i, y_{t+1}=j)
@@ -81,12 +102,15 @@ __global__ void crf_fwd_kernel(const float* __restrict__ emis,  // [B,L,T]
     // cur[jj] = e[t+1][jj] + beta[t+1][jj]; each lane jj<T holds its own;
     // every lane needs all -> read via __shfl
     const float mine = act ? e[(t + 1) * T + j] + beta : NEG;
+    kd += (double)p_prev - (double)alpha[t * T];
+    const float k = (float)kd;
     float m = NEG, s = 0.f;
     float row[TMAX];  // trans[i=lane][jj] + cur[jj]
 #pragma unroll
     for (int jj = 0; jj < TMAX; ++jj) {
       if (jj < T) {
       const float cur = __shfl(mine, jj);
+      if (jj == 0) p_prev = cur;  // cur[0]: D(t) = D(t+1) + cur[0]
       const float v = (act ? tr_s[j * T + jj] : NEG) + cur;
       row[jj] = v;
       m = fmaxf(m, v);
@@ -98,21 +122,21 @@ __global__ void crf_fwd_kernel(const float* __restrict__ emis,  // [B,L,T]
       s += __expf(row[jj] - m);
       }
     }
-    const float beta_t = act ? m + __logf(s) : NEG;  // beta[t][i=lane]
+    const float lse = m + __logf(s);  // beta[t][i=lane] - D(t+1)
     // expected pairwise counts: P(y_t=i, y_{t+1}=jj)
     if (act) {
       const float a_ti = alpha[t * T + j];  // lane = i here
 #pragma unroll
       for (int jj = 0; jj < TMAX; ++jj) {
         if (jj < T) {
-        exp_row[jj] += __expf(a_ti + row[jj] - logZ);
+        exp_row[jj] += __expf(a_ti + row[jj] + k);
         }
       }
       // token marginal at t for tag i=lane
-      const float marg = __expf(a_ti + beta_t - logZ);
+      const float marg = __expf(a_ti + lse + k);
       de[t * T + j] = ((j == tg[t]) ? 1.f : 0.f) - marg;
     }
-    beta = beta_t;
+    beta = act ? lse - p_prev : NEG;
   }
   // gold pair counts minus expected -> dtrans[b]
   if (act) {
@@ -171,41 +195,56 @@ __global__ void crf_fwd_kernel_x4(const float* __restrict__ emis,
   const int b = blockIdx.x * nw * 4 + wid * 4 + g;
   if (b >= B) return;
   const int n = lens[b];
-  if (n <= 0) return;
+  if (n <= 0) {  // empty row: ll is 0, demis/dtrans stay zero
+    if ((lane & 15) == 0) ll[b] = 0.f;
+    return;
+  }
   const float* e = emis + (long)b * L * T;
   const int* tg = tags + (long)b * L;
   float* alpha = alpha_all + (long)(wid * 4 + g) * L * T;
   const int j = lane & 15;
   const bool act = j < T;
 
+  // alpha and beta relative to running offsets (C, D, kd), as in
+  // crf_fwd_kernel
   if (act) alpha[j] = e[j];
   for (int t = 1; t < n; ++t) {
     float m = NEG;
     if (act) {
+      const float ea = e[t * T + j] - alpha[(t - 1) * T];
       for (int i = 0; i < T; ++i)
         m = fmaxf(m, alpha[(t - 1) * T + i] + tr_s[i * T + j]);
       float s = 0.f;
       for (int i = 0; i < T; ++i)
         s += __expf(alpha[(t - 1) * T + i] + tr_s[i * T + j] - m);
-      alpha[t * T + j] = m + __logf(s) + e[t * T + j];
+      alpha[t * T + j] = m + __logf(s) + ea;
     }
   }
   float av = act ? alpha[(n - 1) * T + j] : NEG;
   const float mz = group16_reduce_max(av);
   const float sz = group16_reduce_sum(act ? __expf(av - mz) : 0.f);
-  const float logZ = mz + __logf(sz);
+  const float lz = mz + __logf(sz);
 
-  if (j == 0) {
-    float sc = e[tg[0]];
-    for (int t = 1; t < n; ++t)
+  {  // gold score and C(n-1): the group's 16 lanes stride over t
+    float sc = 0.f;
+    double c_off = 0.0;
+    for (int t = 1 + j; t < n; t += 16) {
       sc += tr_s[tg[t - 1] * T + tg[t]] + e[t * T + tg[t]];
-    ll[b] = sc - logZ;
+      c_off += (double)alpha[(t - 1) * T];
+    }
+    sc = group16_reduce_sum(sc);
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) c_off += __shfl_xor(c_off, off);
+    if (j == 0)
+      ll[b] = (float)((double)(e[tg[0]] + sc) - (c_off + (double)lz));
   }
 
   float* de = demis + (long)b * L * T;
   float beta = 0.f;
+  double kd = -(double)lz;
+  float p_prev = 0.f;
   if (act) {
-    const float marg = __expf(alpha[(n - 1) * T + j] + beta - logZ);
+    const float marg = __expf(alpha[(n - 1) * T + j] + beta - lz);
     de[(n - 1) * T + j] = ((j == tg[n - 1]) ? 1.f : 0.f) - marg;
   }
   float exp_row[T16];
@@ -213,12 +252,15 @@ __global__ void crf_fwd_kernel_x4(const float* __restrict__ emis,
   for (int q = 0; q < T16; ++q) exp_row[q] = 0.f;
   for (int t = n - 2; t >= 0; --t) {
     const float mine = act ? e[(t + 1) * T + j] + beta : NEG;
+    kd += (double)p_prev - (double)alpha[t * T];
+    const float k = (float)kd;
     float m = NEG, s = 0.f;
     float row[T16];
 #pragma unroll
     for (int jj = 0; jj < T16; ++jj) {
       if (jj < T) {
         const float cur = __shfl(mine, base + jj);
+        if (jj == 0) p_prev = cur;
         const float v = (act ? tr_s[j * T + jj] : NEG) + cur;
         row[jj] = v;
         m = fmaxf(m, v);
@@ -227,16 +269,16 @@ __global__ void crf_fwd_kernel_x4(const float* __restrict__ emis,
 #pragma unroll
     for (int jj = 0; jj < T16; ++jj)
       if (jj < T) s += __expf(row[jj] - m);
-    const float beta_t = act ? m + __logf(s) : NEG;
+    const float lse = m + __logf(s);
     if (act) {
       const float a_ti = alpha[t * T + j];
 #pragma unroll
       for (int jj = 0; jj < T16; ++jj)
-        if (jj < T) exp_row[jj] += __expf(a_ti + row[jj] - logZ);
-      const float marg = __expf(a_ti + beta_t - logZ);
+        if (jj < T) exp_row[jj] += __expf(a_ti + row[jj] + k);
+      const float marg = __expf(a_ti + lse + k);
       de[t * T + j] = ((j == tg[t]) ? 1.f : 0.f) - marg;
     }
-    beta = beta_t;
+    beta = act ? lse - p_prev : NEG;
   }
   if (act) {
     float gold[T16];

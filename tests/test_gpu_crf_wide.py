@@ -1,6 +1,11 @@
 """Wide-tagset CRF kernels (csrc/crf_wide.hip): 21..64 tags, and <= 20
 tags at lengths whose alpha the narrow kernels cannot hold in LDS. The
-reference is ops.reference on the same device in fp32."""
+reference is ops.reference on the same device in fp32.
+
+(3, 512, 20) is a wide case for the loss only: its int8 backpointers fit in
+LDS, so crf_viterbi decodes it with the narrow one-per-wave
+crf_viterbi_kernel of crf.hip. The other narrow cases are in
+test_gpu_crf_narrow.py."""
 import pytest
 import torch
 
@@ -90,6 +95,8 @@ def test_crf_wide_empty_row_is_zero():
     assert torch.count_nonzero(pred[1]) == 0
 
 
+# (3, 512, 20) runs crf.hip's crf_viterbi_kernel, not a wide kernel: the
+# decode leaves crf.hip only for T > 20
 @pytest.mark.parametrize("B,L,T", [(7, 50, 24), (5, 45, 64), (2, 512, 64),
                                    (3, 512, 20)])
 def test_crf_wide_viterbi_matches_reference(B, L, T):

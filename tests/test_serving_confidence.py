@@ -18,8 +18,11 @@ def _feats(rng, batch, seq=32):
 
 def _engine(tmp_path, confidence, **kw):
     from chinesener_amd.serve.engine import InferenceEngine
+    # device="cpu": this file is the CPU side (the direct model call below
+    # feeds CPU tensors), also on a machine that has a GPU
     return InferenceEngine("bilstm_crf", str(tmp_path), use_graph=False,
-                           max_seq_len=32, confidence=confidence, **kw)
+                           max_seq_len=32, confidence=confidence,
+                           device="cpu", **kw)
 
 
 def test_engine_predict_scored_matches_model(tmp_path):
