@@ -85,10 +85,10 @@ class BertLayer(nn.Module):
         x = ops.linear_dropout_add_layernorm(
             ctx, self.attn_out.weight, self.attn_out.bias, x, self.ln1_w,
             self.ln1_b, self.eps, self.p_drop, self.training)
-        f = ops.bias_gelu(ops.linear(x, self.ffn_in.weight), self.ffn_in_bias)
-        return ops.linear_dropout_add_layernorm(
-            f, self.ffn_out.weight, self.ffn_out.bias, x, self.ln2_w,
-            self.ln2_b, self.eps, self.p_drop, self.training)
+        return ops.ffn_gelu_dropout_add_layernorm(
+            x, self.ffn_in.weight, self.ffn_in_bias, self.ffn_out.weight,
+            self.ffn_out.bias, x, self.ln2_w, self.ln2_b, self.eps,
+            self.p_drop, self.training)
 
 
 class BertModel(nn.Module):

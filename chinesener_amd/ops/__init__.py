@@ -55,7 +55,7 @@ def get_ext():
 
 from .functional import (  # noqa: E402,F401
     attention, attention_qkv, bias_gelu, add_layernorm, dropout_add_layernorm,
-    embed3,
+    embed3, ffn_gelu_dropout_add_layernorm,
     layernorm, linear, linear_attention_qkv, linear_dropout_add_layernorm,
     crf_nll,
     crf_viterbi, crf_path_posterior, crf_decode_scored, token_path_scores,

@@ -170,10 +170,10 @@ def _med_time(fn):
     return sorted(ts)[1]
 
 
-def _pick2(key, fn_ours, fn_lib) -> bool:
+def _pick2(key, fn_ours, fn_lib, min_recur: int = _PICK_MIN_RECUR) -> bool:
     """Measured dispatch between two GEMM paths: once the library's
     TunableOp tuning is done, time both (median of 5) and cache the
-    winner."""
+    winner. min_recur: how often the key must have been seen first."""
     hit = _GEMM_NT_CHOICE.get(key)
     if hit is not None:
         return hit
@@ -181,7 +181,7 @@ def _pick2(key, fn_ours, fn_lib) -> bool:
         return False               # never measure now; decide later
     n = _GEMM_NT_CALLS.get(key, 0) + 1
     _GEMM_NT_CALLS[key] = n
-    if n < _PICK_MIN_RECUR:
+    if n < min_recur:
         return False               # shape hasn't proven it recurs
 
     t_ours, t_lib = _med_time(fn_ours), _med_time(fn_lib)
@@ -433,6 +433,152 @@ def bias_gelu(x, bias):
         y = _BiasGeluFn.apply(x.reshape(-1, shape[-1]).contiguous(), bias)
         return y.reshape(shape)
     return ref.bias_gelu(x, bias)
+
+
+# ------------------------------------------------------------- fused FFN
+def _fused_gelu_mode() -> str:
+    """'auto' (default): race each fused FFN GEMM (bias+GELU, or its
+    backward, in the epilogue) against the GEMM + elementwise pair it
+    replaces, per shape and per half; 'force': always fused; 'off': the
+    unfused composition, launch for launch."""
+    return os.environ.get("CHINESENER_FUSED_GELU", "auto")
+
+
+def _inner_decided(key) -> bool:
+    """The GEMM dispatch the unfused pair would go through has settled
+    (or is not measured at all), so a race against it is meaningful."""
+    return _gemm_nt_mode() != "auto" or key in _GEMM_NT_CHOICE
+
+
+def _pick_fused(key, inner_key, fn_fused, fn_pair) -> bool:
+    mode = _fused_gelu_mode()
+    if mode != "auto":
+        return mode == "force"
+    if key not in _GEMM_NT_CHOICE and not _inner_decided(inner_key):
+        return False
+    # the inner key only got decided because the shape recurs: race at the
+    # first call that is neither captured nor under library tuning
+    return _pick2(key, fn_fused, fn_pair, min_recur=1)
+
+
+def _ffn_up(x2, w1, b1, save_pre: bool):
+    """(u, g) = (x2 @ w1^T, gelu(u + b1)); u is None without save_pre on
+    the fused path. x2: contiguous [M, K]."""
+    ext = get_ext()
+    M, K = x2.shape
+    N = w1.shape[0]
+
+    def fused():
+        return ext.gemm_nt_bias_gelu(x2, w1, b1, save_pre)
+
+    def pair():
+        u = _linear_fwd(x2, w1, None)
+        return u, ext.bias_gelu_fwd(u, b1)
+
+    key = ("ffn_up_gelu" if save_pre else "ffn_up_gelu_nopre", M, N, K)
+    if _pick_fused(key, (M, N, K, False), fused, pair):
+        u, g = fused()
+        return u, g
+    return pair()
+
+
+def _ffn_dn(dx_drop, w2, u, b1):
+    """(du, db1) = ((dx_drop @ w2) * gelu'(u + b1), colsum(du)).
+    dx_drop: contiguous [M, N]; w2 [N, K] as stored; u [M, K]."""
+    ext = get_ext()
+    M, N = dx_drop.shape
+    K = w2.shape[1]
+
+    def fused():
+        return ext.gemm_nn_dgelu(dx_drop, w2, u, b1)
+
+    def pair():
+        return ext.bias_gelu_bwd(_linear_dgrad(dx_drop, u, w2), u, b1)
+
+    if _pick_fused(("ffn_dn_dgelu", M, N, K), ("dx", M, N, K), fused, pair):
+        du, db1 = fused()
+        return du, db1
+    du, db1 = pair()
+    return du, db1
+
+
+class _FfnGeluFn(torch.autograd.Function):
+    """LayerNorm(dropout(gelu(x @ w1^T + b1) @ w2^T + b2) + residual) as
+    one node, so that the pre-activation u never makes a round trip
+    through an elementwise kernel: forward, FFN-up writes u and gelu(u +
+    b1) from one epilogue; backward, the FFN-down dgrad applies gelu'
+    and emits the b1 gradient from its epilogue. Each half falls back to
+    the unfused pair of kernels when that measures faster."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, res, ln_w, ln_b, eps, keep):
+        x2 = x.reshape(-1, x.shape[-1])
+        u, g = _ffn_up(x2, w1, b1, True)
+        a = _linear_fwd(g, w2, b2)
+        y, s, mask, mean, rstd = get_ext().dropout_add_ln_fwd(
+            a, res, ln_w, ln_b, eps, keep, _rng_counter_for(x.device))
+        ctx.save_for_backward(x, w1, b1, w2, u, g, s, ln_w, mask, mean, rstd)
+        ctx.keep = keep
+        ctx.has_bias = b2 is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, b1, w2, u, g, s, ln_w, mask, mean, rstd = ctx.saved_tensors
+        dsum, dx_drop, dw_ln, db_ln, db2 = get_ext().dropout_add_ln_bwd(
+            dy.contiguous(), s, ln_w, mean, rstd, mask, ctx.keep,
+            ctx.has_bias)
+        dw2 = _linear_wgrad(dx_drop, g, w2)
+        du, db1 = _ffn_dn(dx_drop, w2, u, b1)
+        dw1 = _linear_wgrad(du, x, w1)
+        dx = _linear_dgrad(du, x, w1)
+        return dx, dw1, db1, dw2, db2, dsum, dw_ln, db_ln, None, None
+
+
+def _ffn_fusable(x, w1, b1, w2, b2) -> bool:
+    """Operands the fused FFN GEMMs take as stored: pure bf16 on the GPU,
+    full 128-tiles, a bf16 or fp32 bias."""
+    if not (hip_enabled(x) and _fused_gelu_mode() != "off"
+            and not torch.is_autocast_enabled()):
+        return False
+    M = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    return (x.dtype == torch.bfloat16 and w1.dtype == x.dtype
+            and w2.dtype == x.dtype and x.is_contiguous()
+            and w1.is_contiguous() and w2.is_contiguous()
+            and b1 is not None and b1.is_contiguous()
+            and b1.dtype in (torch.bfloat16, torch.float32)
+            and (b2 is None or b2.dtype == x.dtype)
+            and M > 0 and M % 128 == 0 and w1.shape[0] % 128 == 0
+            and w1.shape[1] % 128 == 0 and w2.shape[0] == w1.shape[1]
+            and w2.shape[1] == w1.shape[0])
+
+
+def ffn_gelu_dropout_add_layernorm(x, w1, b1, w2, b2, residual, ln_w, ln_b,
+                                   eps: float = 1e-12, p: float = 0.1,
+                                   training: bool = True):
+    """The BERT feed-forward sublayer, LayerNorm(dropout(gelu(x w1^T + b1)
+    w2^T + b2) + residual). Training in pure bf16 on the GPU runs it as
+    one autograd node whose two GELU passes live in GEMM epilogues (see
+    _FfnGeluFn); without grad only the forward epilogue is used and the
+    pre-activation is never written. Everything else is the composition
+    of the public ops, unchanged."""
+    if _ffn_fusable(x, w1, b1, w2, b2):
+        if (training and p > 0 and torch.is_grad_enabled()
+                and os.environ.get("CHINESENER_NO_FUSED_DROPOUT") != "1"):
+            H = w2.shape[0]
+            y = _FfnGeluFn.apply(
+                x, w1, b1, w2, b2,
+                residual.to(x.dtype).reshape(-1, H).contiguous(),
+                ln_w, ln_b, eps, 1.0 - p)
+            return y.reshape(*x.shape[:-1], H)
+        if not torch.is_grad_enabled():
+            _, f = _ffn_up(x.reshape(-1, x.shape[-1]), w1, b1, False)
+            return linear_dropout_add_layernorm(
+                f.reshape(*x.shape[:-1], w1.shape[0]), w2, b2, residual,
+                ln_w, ln_b, eps, p, training)
+    f = bias_gelu(linear(x, w1), b1)
+    return linear_dropout_add_layernorm(f, w2, b2, residual, ln_w, ln_b,
+                                        eps, p, training)
 
 
 # ------------------------------------------------------------ attention

@@ -40,6 +40,11 @@ at::Tensor gemm_nt(const at::Tensor&, const at::Tensor&,
                    c10::optional<at::Tensor>, bool);
 at::Tensor gemm_tn(const at::Tensor&, const at::Tensor&, long, bool);
 at::Tensor gemm_nn(const at::Tensor&, const at::Tensor&, bool);
+std::vector<at::Tensor> gemm_nt_bias_gelu(const at::Tensor&,
+                                          const at::Tensor&,
+                                          const at::Tensor&, bool);
+std::vector<at::Tensor> gemm_nn_dgelu(const at::Tensor&, const at::Tensor&,
+                                      const at::Tensor&, const at::Tensor&);
 at::Tensor embed3_fwd(const at::Tensor&, const at::Tensor&,
                       const at::Tensor&, const at::Tensor&,
                       const at::Tensor&);
@@ -180,6 +185,10 @@ PYBIND11_MODULE(_hip_ops, m) {
         py::arg("split") = 0, py::arg("fp32_out") = false);
   m.def("gemm_nn", &gemm_nn, py::arg("a"), py::arg("b"),
         py::arg("fp32_out") = false);
+  m.def("gemm_nt_bias_gelu", &gemm_nt_bias_gelu, py::arg("a"), py::arg("b"),
+        py::arg("bias"), py::arg("save_pre") = true);
+  m.def("gemm_nn_dgelu", &gemm_nn_dgelu, py::arg("a"), py::arg("b"),
+        py::arg("u"), py::arg("bias"));
   m.def("embed3_fwd", &embed3_fwd);
   m.def("crf_fwd", &crf_fwd);
   m.def("crf_viterbi", &crf_viterbi);

@@ -17,6 +17,8 @@
 // N%128==0, K%64==0 (every BERT shape: K/N in {768, 2304, 3072},
 // M = batch*seq); anything else falls back to the library GEMM.
 #include "common.h"
+#include "gelu.h"
+#include "slab_colsum.h"
 
 #define BM 128
 #define BN 128
@@ -500,4 +502,370 @@ at::Tensor gemm_nn(const at::Tensor& a, const at::Tensor& b, bool fp32_out) {
               "gemm_nn: needs M%128==0, N%128==0, K%64==0 (got ", M, "x", N,
               "x", K, ")");
   return launch_gemm_ks<true>(a, b, M, N, K, 1, fp32_out);
+}
+
+// ===================================================================
+// FFN GEMMs with the bias+GELU passes in their epilogues:
+//   gemm_nt_bias_gelu: u = bf16(A @ B^T),  g = bf16(gelu(u + bias))
+//   gemm_nn_dgelu:     dh = bf16(A @ B),   du = bf16(dh * gelu'(u + bias)),
+//                      dbias = column sums of float(du)
+// Sibling kernels of gemm_nt_kernel / gemm_ks_kernel<true>: same staging,
+// same fragments, same K order. The one change in the loop is that the
+// two MFMA operands trade places (D^T = B-frag x A-frag), which makes the
+// C/D map  row m = lane & 15, columns n = (lane >> 4) * 4 + r: a lane
+// owns 4 CONSECUTIVE columns of one row, so u is loaded and u / g / du
+// are stored 8 bytes per lane (16 instead of 64 store instructions per
+// wave and tile), straight from registers: no LDS round trip and no
+// barrier in the forward epilogue. Each product a*b and the order in
+// which an element's K terms are added are those of the plain kernels,
+// and the rounding to bf16 before the bias is kept, so u, g and du are
+// what gemm_nt -> bias_gelu_fwd and gemm_nn -> bias_gelu_bwd produce.
+
+template <bool SAVE_PRE, typename BT>
+__global__ __launch_bounds__(256, 2) void gemm_nt_gelu_kernel(
+    const bf16* __restrict__ A,   // [M, K]
+    const bf16* __restrict__ B,   // [N, K]
+    const BT* __restrict__ bias,  // [N]
+    bf16* __restrict__ U,         // [M, N] pre-activation (SAVE_PRE)
+    bf16* __restrict__ G,         // [M, N] gelu(u + bias)
+    long M, long N, long K, int tiles_n) {
+  __shared__ bf16 smem[2 * 2 * BM * BK];
+  bf16* a_s = smem;
+  bf16* b_s = smem + 2 * BM * BK;
+
+  const int nwg = gridDim.x;
+  int wg = blockIdx.x;
+  {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = wg & 7, idx = wg >> 3;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const long m0 = (long)(wg / tiles_n) * BM;
+  const long n0 = (long)(wg % tiles_n) * BN;
+
+  const int wid = threadIdx.x / WAVE;
+  const int wr = (wid >> 1) * 64, wc = (wid & 1) * 64;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g4 = (lane >> 4) << 2;
+
+  cfrag acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = cfrag{0.f, 0.f, 0.f, 0.f};
+
+  stage_tile(A, K, m0, 0, a_s);
+  stage_tile(B, K, n0, 0, b_s);
+  // this lane's 16 bias values, in flight under the first stage
+  float be[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) load_bias4(bias, n0 + wc + j * 16 + g4, be[j]);
+  __syncthreads();
+
+  const int nkt = (int)(K / BK);
+  int buf = 0;
+  for (int kt = 0; kt < nkt; ++kt) {
+    if (kt + 1 < nkt) {
+      const int nxt = buf ^ 1;
+      stage_tile(A, K, m0, (long)(kt + 1) * BK, a_s + nxt * BM * BK);
+      stage_tile(B, K, n0, (long)(kt + 1) * BK, b_s + nxt * BM * BK);
+    }
+    const bf16* at = a_s + buf * BM * BK;
+    const bf16* bt = b_s + buf * BM * BK;
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+      bfrag af[4], bfr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = frag(at, wr + i * 16, kk * 32);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bfr[j] = frag(bt, wc + j * 16, kk * 32);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // epilogue: acc[i][j][r] = C[m0+wr+16i + (lane&15)][n0+wc+16j + g4 + r]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row = m0 + wr + i * 16 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long off = row * N + n0 + wc + j * 16 + g4;
+      bf16 uo[4], go[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        from_f32(acc[i][j][r], &uo[r]);
+        const float u = to_f32(uo[r]) + be[j][r];
+        from_f32(gelu_f(u), &go[r]);
+      }
+      if (SAVE_PRE)
+        *reinterpret_cast<s16x4*>(U + off) = *reinterpret_cast<s16x4*>(uo);
+      *reinterpret_cast<s16x4*>(G + off) = *reinterpret_cast<s16x4*>(go);
+    }
+  }
+}
+
+// slab: [M / 128][N] fp32, row = this block's tile row; every block
+// writes all 128 columns of its tile, so the slab needs no zero-fill.
+template <typename BT>
+__global__ __launch_bounds__(256, 2) void gemm_nn_dgelu_kernel(
+    const bf16* __restrict__ A,   // [M, K]  upstream gradient
+    const bf16* __restrict__ B,   // [K, N]  weight as stored
+    const bf16* __restrict__ U,   // [M, N]  saved pre-activation
+    const BT* __restrict__ bias,  // [N]
+    bf16* __restrict__ DU,        // [M, N]
+    float* __restrict__ slab, long M, long N, long K, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * BM * BK];
+  bf16* a_s = smem;
+  bf16* b_s = smem + 2 * BM * BK;
+
+  const int nwg = gridDim.x;
+  int wg = blockIdx.x;
+  {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = wg & 7, idx = wg >> 3;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int tile_m = wg / tiles_n;
+  const long m0 = (long)tile_m * BM;
+  const long n0 = (long)(wg % tiles_n) * BN;
+
+  const int wid = threadIdx.x / WAVE;
+  const int wr = (wid >> 1) * 64, wc = (wid & 1) * 64;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g8 = (lane >> 4) << 3;
+  const int g4 = (lane >> 4) << 2;
+
+  int boff[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    boff[j][0] = tr_off(g8, wc + j * 16);
+    boff[j][1] = tr_off(g8 + 4, wc + j * 16);
+  }
+
+  cfrag acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = cfrag{0.f, 0.f, 0.f, 0.f};
+
+  const int nkt = (int)(K / BK);
+  // the stage whose barrier also drains the u loads: two before the end
+  const int kpre = nkt >= 2 ? nkt - 2 : 0;
+  s16x4 uraw[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) uraw[i][j] = s16x4{0, 0, 0, 0};
+
+  stage_tile(A, K, m0, 0, a_s);
+  stage_tile_ks(B, N, 0, n0, b_s);
+  float be[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) load_bias4(bias, n0 + wc + j * 16 + g4, be[j]);
+  __syncthreads();
+
+  // stage order as in gemm_ks_kernel: fragments, then the prefetch, then
+  // the MFMAs
+  int buf = 0;
+  for (int kt = 0; kt < nkt; ++kt) {
+    const bf16* at = a_s + buf * BM * BK;
+    const bf16* bt = b_s + buf * BM * BK;
+    bfrag af[BK / 32][4], bfr[BK / 32][4];
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[kk][i] = frag(at, wr + i * 16, kk * 32);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bfr[kk][j] = frag_tr(bt + kk * 32 * 128, boff[j][0], boff[j][1]);
+    }
+    if (kt + 1 < nkt) {
+      const int nxt = buf ^ 1;
+      const long k1 = (long)(kt + 1) * BK;
+      stage_tile(A, K, m0, k1, a_s + nxt * BM * BK);
+      stage_tile_ks(B, N, k1, n0, b_s + nxt * BM * BK);
+    }
+    if (kt == kpre) {                        // u: 16 x 8 bytes per lane
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long row = m0 + wr + i * 16 + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          uraw[i][j] = *reinterpret_cast<const s16x4*>(
+              U + row * N + n0 + wc + j * 16 + g4);
+      }
+    }
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = mfma16(bfr[kk][j], af[kk][i], acc[i][j]);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // epilogue: du from registers; cs[j][r] = this lane's 4 rows of column
+  // n0 + wc + 16j + g4 + r
+  float cs[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cs[j][r] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row = m0 + wr + i * 16 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bf16 o[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bf16 dh;
+        from_f32(acc[i][j][r], &dh);
+        const float u =
+            to_f32(reinterpret_cast<const bf16*>(&uraw[i][j])[r]) + be[j][r];
+        const float g = to_f32(dh);
+        from_f32(g * dgelu_f(u), &o[r]);
+        cs[j][r] += to_f32(o[r]);
+      }
+      *reinterpret_cast<s16x4*>(DU + row * N + n0 + wc + j * 16 + g4) =
+          *reinterpret_cast<s16x4*>(o);
+    }
+  }
+  // column sums over the tile's 128 rows in a fixed order: the lane's 4
+  // rows above, the 16 lanes of a group (xor tree), then the lower wave
+  // row + the upper one through LDS (free after the loop's last barrier)
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cs[j][r] = group16_reduce_sum(cs[j][r]);
+  float* red = reinterpret_cast<float*>(smem);         // [128] columns
+  if ((wid >> 1) == 1 && (lane & 15) == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *reinterpret_cast<f32x4*>(red + wc + j * 16 + g4) =
+          f32x4{cs[j][0], cs[j][1], cs[j][2], cs[j][3]};
+  }
+  __syncthreads();
+  if ((wid >> 1) == 0 && (lane & 15) == 0) {
+    float* srow = slab + (long)tile_m * N + n0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(red + wc + j * 16 + g4);
+      *reinterpret_cast<f32x4*>(srow + wc + j * 16 + g4) =
+          f32x4{cs[j][0] + hi[0], cs[j][1] + hi[1], cs[j][2] + hi[2],
+                cs[j][3] + hi[3]};
+    }
+  }
+}
+
+static void check_ffn_bias(const at::Tensor& bias, long N, const char* who) {
+  TORCH_CHECK(bias.is_cuda() && bias.is_contiguous() && bias.dim() == 1 &&
+                  bias.numel() == N &&
+                  (bias.scalar_type() == at::kFloat ||
+                   bias.scalar_type() == at::kBFloat16),
+              who, ": bias must be a contiguous fp32 or bf16 [N]");
+}
+
+// (u, g) = (A @ B^T, gelu(u + bias)), both bf16; save_pre=false writes
+// only g and returns an undefined u.
+std::vector<at::Tensor> gemm_nt_bias_gelu(const at::Tensor& a,
+                                          const at::Tensor& b,
+                                          const at::Tensor& bias,
+                                          bool save_pre) {
+  CHECK_CUDA_CONTIG(a);
+  CHECK_CUDA_CONTIG(b);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 &&
+                  a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              "gemm_nt_bias_gelu: 2-D bf16 operands");
+  const long M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(b.size(1) == K, "gemm_nt_bias_gelu: K mismatch");
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 &&
+                  K % BK == 0,
+              "gemm_nt_bias_gelu: needs M%128==0, N%128==0, K%64==0 (got ",
+              M, "x", N, "x", K, ")");
+  check_ffn_bias(bias, N, "gemm_nt_bias_gelu");
+  at::Tensor u;
+  if (save_pre) u = at::empty({M, N}, a.options());
+  auto g = at::empty({M, N}, a.options());
+  const dim3 grid((unsigned)((M / BM) * (N / BN)));
+  const bf16* ap = (const bf16*)a.data_ptr();
+  const bf16* bp = (const bf16*)b.data_ptr();
+  bf16* up = save_pre ? (bf16*)u.data_ptr() : nullptr;
+  bf16* gp = (bf16*)g.data_ptr();
+  const int tn = (int)(N / BN);
+  auto st = cur_stream(a);
+  const bool bb = bias.scalar_type() == at::kBFloat16;
+#define LAUNCH_NT_GELU(SP, BT)                                               \
+  hipLaunchKernelGGL((gemm_nt_gelu_kernel<SP, BT>), grid, dim3(256), 0, st,  \
+                     ap, bp, (const BT*)bias.data_ptr(), up, gp, M, N, K, tn)
+  if (save_pre) {
+    if (bb) LAUNCH_NT_GELU(true, bf16); else LAUNCH_NT_GELU(true, float);
+  } else {
+    if (bb) LAUNCH_NT_GELU(false, bf16); else LAUNCH_NT_GELU(false, float);
+  }
+#undef LAUNCH_NT_GELU
+  HIP_CHECK_LAST();
+  return {u, g};
+}
+
+// (du, dbias) = ((A @ B) * gelu'(u + bias), column sums of du); du bf16,
+// dbias in the bias dtype.
+std::vector<at::Tensor> gemm_nn_dgelu(const at::Tensor& a,
+                                      const at::Tensor& b,
+                                      const at::Tensor& u,
+                                      const at::Tensor& bias) {
+  CHECK_CUDA_CONTIG(a);
+  CHECK_CUDA_CONTIG(b);
+  CHECK_CUDA_CONTIG(u);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && u.dim() == 2 &&
+                  a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16 &&
+                  u.scalar_type() == at::kBFloat16,
+              "gemm_nn_dgelu: 2-D bf16 operands");
+  const long M = a.size(0), K = a.size(1), N = b.size(1);
+  TORCH_CHECK(b.size(0) == K, "gemm_nn_dgelu: K mismatch");
+  TORCH_CHECK(u.size(0) == M && u.size(1) == N,
+              "gemm_nn_dgelu: u must be [M, N]");
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 &&
+                  K % BK == 0,
+              "gemm_nn_dgelu: needs M%128==0, N%128==0, K%64==0 (got ", M,
+              "x", N, "x", K, ")");
+  check_ffn_bias(bias, N, "gemm_nn_dgelu");
+  auto du = at::empty({M, N}, a.options());
+  auto slab = at::empty({M / BM, N}, a.options().dtype(at::kFloat));
+  auto dbias = at::empty({N}, bias.options());
+  const dim3 grid((unsigned)((M / BM) * (N / BN)));
+  auto st = cur_stream(a);
+  if (bias.scalar_type() == at::kBFloat16) {
+    hipLaunchKernelGGL((gemm_nn_dgelu_kernel<bf16>), grid, dim3(256), 0, st,
+                       (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
+                       (const bf16*)u.data_ptr(),
+                       (const bf16*)bias.data_ptr(), (bf16*)du.data_ptr(),
+                       slab.data_ptr<float>(), M, N, K, (int)(N / BN));
+    launch_slab_colsum<bf16, bf16>(slab, dbias.data_ptr(), (int)N, nullptr,
+                                   st);
+  } else {
+    hipLaunchKernelGGL((gemm_nn_dgelu_kernel<float>), grid, dim3(256), 0, st,
+                       (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
+                       (const bf16*)u.data_ptr(), bias.data_ptr<float>(),
+                       (bf16*)du.data_ptr(), slab.data_ptr<float>(), M, N, K,
+                       (int)(N / BN));
+    launch_slab_colsum<float, float>(slab, dbias.data_ptr(), (int)N, nullptr,
+                                     st);
+  }
+  HIP_CHECK_LAST();
+  return {du, dbias};
 }
