@@ -116,6 +116,61 @@ def decode_prediction_scored(tokens: Sequence[str], tags: Sequence[str],
     return out
 
 
+def decode_prediction_nbest(tokens: Sequence[str],
+                            tag_paths: Sequence[Sequence[str]],
+                            logp: Sequence[float], offset: int = 0) -> Dict:
+    """The n best taggings of one sentence as entity lists, and what they
+    say together about each entity.
+
+    ``tag_paths[r]`` is the tag sequence of rank r over one model row and
+    ``logp[r]`` its log posterior (one row of the model's nbest paths, ids
+    mapped to tags, and nbest_logp); ``offset`` is the shift between
+    ``tokens`` and that row (1 when the row starts with [CLS]). Ranks the
+    row does not have (logp = -inf) are skipped.
+
+    Returns {"alternatives": [{"rank", "prob", "entities": [{"type", "text",
+    "start", "end"}]}], "entities": [{"type", "text", "start", "end",
+    "support"}]}: the alternatives in rank order with prob = exp(min(0,
+    logp)), then every distinct well-formed entity in order of first
+    appearance (rank, then position) with
+
+        support = min(1, sum of prob over the alternatives that contain
+                         exactly this (type, start, end) with no error flag)
+
+    start/end index ``tokens``, end inclusive. The alternatives are
+    distinct paths, so their probabilities add, and each one that holds the
+    entity holds it as a strict BIO entity: support is a lower bound on the
+    strict entity posterior (decode_prediction_scored's confidence is an
+    upper bound). Spans with a B/I type mismatch ('[ERROR]' surface) are
+    listed in their alternative but earn no support. Neither does a span
+    that opens with I- where the entity's first (best-ranked) occurrence
+    opens with B-, or the other way round: it is the same (type, start,
+    end) but another tag sequence, which the confidence does not cover, so
+    counting it could lift support above that upper bound."""
+    toks = fix_tokens(tokens)
+    alternatives, support, first, opening = [], {}, {}, {}
+    for rank, (path, lp) in enumerate(zip(tag_paths, logp)):
+        lp = float(lp)
+        if lp == -math.inf or math.isnan(lp):
+            continue
+        tags = list(path)[offset:offset + len(toks)]
+        prob = math.exp(min(0.0, lp))
+        ents = []
+        for etype, start, end, err in _bio_groups(tags):
+            ent = {"type": etype, "text": _surface(toks, start, end, err),
+                   "start": start, "end": end}
+            ents.append(ent)
+            if not err:
+                key = (etype, start, end)
+                first.setdefault(key, ent)
+                if opening.setdefault(key, tags[start][:2]) == tags[start][:2]:
+                    support[key] = support.get(key, 0.0) + prob
+        alternatives.append({"rank": rank, "prob": prob, "entities": ents})
+    entities = [dict(ent, support=min(1.0, support[key]))
+                for key, ent in first.items()]
+    return {"alternatives": alternatives, "entities": entities}
+
+
 def extract_entity(tokens: Sequence[str], tags: Sequence[str]) -> Dict[str, set]:
     """Like decode_prediction but deduplicated per type (reference
     tools/infer_utils.py:76-99 returns {type: {surfaces}})."""

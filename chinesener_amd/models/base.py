@@ -19,6 +19,9 @@ class ModelOutput(NamedTuple):
     # (span_a, span_b), fp64 [B,L]: log P(tags s..e as decoded) =
     # span_a[s] + span_b[e]; filled only with compute_conf=True
     span_scores: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+    # (paths long [B,k,L], scores f32 [B,k], logp f64 [B,k]): the k best tag
+    # paths, best first; filled only with compute_nbest=k > 0
+    nbest: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
 
 
 class NerModel(nn.Module):
@@ -30,9 +33,14 @@ class NerModel(nn.Module):
 
     def forward(self, features: Dict[str, torch.Tensor],
                 compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         """compute_conf=True implies decoding and also fills
-        ModelOutput.span_scores (see ops.crf_path_posterior)."""
+        ModelOutput.span_scores (see ops.crf_path_posterior).
+        compute_nbest=k > 0 implies decoding and also fills
+        ModelOutput.nbest with the k best paths (see ops.crf_nbest).
+        pred_ids stays the Viterbi decode; rank 0 of nbest equals it except
+        under exact score ties."""
         raise NotImplementedError
 
 

@@ -126,12 +126,27 @@ class CRF(nn.Module):
             emissions.float(), mask, self.transitions)
         return pred, (span_a, span_b)
 
+    def decode_nbest(self, emissions, mask, k: int):
+        """(paths long [B,k,L], scores f32 [B,k], logp f64 [B,k]): the k
+        best tag paths, best first, their unnormalised scores and log
+        posteriors (ops.crf_nbest). Ranks a row does not have get -inf and
+        a zero path. Rank 0 is decode()'s path except under exact score
+        ties."""
+        return ops.crf_nbest(emissions.float(), mask, self.transitions, k)
+
     def predict(self, emissions, mask, compute_pred: bool,
-                compute_conf: bool):
-        """The (pred, span_scores) pair a model's forward returns."""
+                compute_conf: bool, *, nbest: int = 0):
+        """The (pred, span_scores, nbest) triple a model's forward returns:
+        pred is decode()'s (None unless anything is asked for), span_scores
+        is filled with compute_conf, nbest is decode_nbest(..., nbest) or
+        None when nbest is 0."""
         if compute_conf:
-            return self.decode_scored(emissions, mask)
-        return (self.decode(emissions, mask) if compute_pred else None), None
+            pred, conf = self.decode_scored(emissions, mask)
+        else:
+            want = compute_pred or nbest > 0
+            pred, conf = (self.decode(emissions, mask) if want else None), None
+        best = self.decode_nbest(emissions, mask, nbest) if nbest > 0 else None
+        return pred, conf, best
 
 
 class TokenEmbedding(nn.Module):

@@ -32,7 +32,8 @@ class MrcBio(NerModel):
         self.logits = nn.Linear(cfg.hidden_size, 3)
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         seq = self.bert(features["token_ids"], features["mask"],
                         features.get("segment_ids"))
         logits = self.logits(self.dropout(seq))
@@ -41,9 +42,14 @@ class MrcBio(NerModel):
         if "label_ids" in features:
             loss = ops.masked_cross_entropy(logits, features["label_ids"],
                                             text_mask)
-        pred, conf = None, None
-        if compute_pred or compute_conf:
+        pred, conf, nbest = None, None, None
+        if compute_pred or compute_conf or compute_nbest > 0:
             pred = logits.argmax(-1) * text_mask
         if compute_conf:
             conf = ops.token_path_scores(logits, text_mask, pred)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        if compute_nbest > 0:
+            # independent tokens: logp is the path score; token_nbest is
+            # position-wise, so the text region after the query is decoded
+            nbest = ops.token_nbest(logits, text_mask, compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)

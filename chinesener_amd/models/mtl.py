@@ -72,7 +72,8 @@ class BertBilstmCrfMtl(NerModel):
         return self.dropout(seq)
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")
@@ -88,26 +89,34 @@ class BertBilstmCrfMtl(NerModel):
         loss = None
         if "label_ids" in features:
             loss = self._mtl_loss(features, logit0, logit1, sample_task, B)
-        pred, conf = self._decode_towers(features["mask"], logit0, logit1,
-                                         sample_task, compute_pred,
-                                         compute_conf)
-        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf)
+        pred, conf, nbest = self._decode_towers(
+            features["mask"], logit0, logit1, sample_task, compute_pred,
+            compute_conf, compute_nbest)
+        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf,
+                           nbest=nbest)
 
     def _decode_towers(self, mask, logit0, logit1, sample_task,
-                       compute_pred, compute_conf):
-        """Both towers decode; each sample keeps its own task's tags, and
-        with compute_conf its own task's span scores."""
-        if not (compute_pred or compute_conf):
-            return None, None
-        p0, c0 = self.tower0.crf.predict(logit0, mask, True, compute_conf)
-        p1, c1 = self.tower1.crf.predict(logit1, mask, True, compute_conf)
+                       compute_pred, compute_conf, compute_nbest=0):
+        """Both towers decode; each sample keeps its own task's tags, with
+        compute_conf its own task's span scores and with compute_nbest its
+        own task's (paths, scores, logp)."""
+        if not (compute_pred or compute_conf or compute_nbest > 0):
+            return None, None, None
+        p0, c0, n0 = self.tower0.crf.predict(logit0, mask, True, compute_conf,
+                                             nbest=compute_nbest)
+        p1, c1, n1 = self.tower1.crf.predict(logit1, mask, True, compute_conf,
+                                             nbest=compute_nbest)
         first = sample_task[:, None] == 0
         pred = torch.where(first, p0, p1)
-        conf = None
+        conf, nbest = None, None
         if compute_conf:
             conf = (torch.where(first, c0[0], c1[0]),
                     torch.where(first, c0[1], c1[1]))
-        return pred, conf
+        if compute_nbest > 0:
+            nbest = (torch.where(first[:, :, None], n0[0], n1[0]),
+                     torch.where(first, n0[1], n1[1]),
+                     torch.where(first, n0[2], n1[2]))
+        return pred, conf, nbest
 
     def _mtl_loss(self, features, logit0, logit1, sample_task, B):
         # per-task masked NLL: -ll per sample, masked by task membership
@@ -152,7 +161,8 @@ class BertBilstmCrfAdv(BertBilstmCrfMtl):
         self.tower1 = TaskTower(in1, hidden, self.label_sizes[1], act, keep)
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")
@@ -178,7 +188,8 @@ class BertBilstmCrfAdv(BertBilstmCrfMtl):
             task_loss = self._mtl_loss(features, logit0, logit1, sample_task, B)
             adv = nn.functional.cross_entropy(adv_logits.float(), sample_task)
             loss = task_loss + self.lam * adv
-        pred, conf = self._decode_towers(features["mask"], logit0, logit1,
-                                         sample_task, compute_pred,
-                                         compute_conf)
-        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf)
+        pred, conf, nbest = self._decode_towers(
+            features["mask"], logit0, logit1, sample_task, compute_pred,
+            compute_conf, compute_nbest)
+        return ModelOutput(loss, pred, task_ids=task_ids, span_scores=conf,
+                           nbest=nbest)

@@ -46,7 +46,8 @@ class BilstmCrf(NerModel):
         return emb
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         lens = _lens(features)
         emb = self.emb_dropout(self.embedding(features["token_ids"]))
         emb = self._enhance(features, emb)
@@ -57,9 +58,11 @@ class BilstmCrf(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
-                                      compute_conf)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        pred, conf, nbest = self.crf.predict(
+            logits, features["mask"], compute_pred, compute_conf,
+            nbest=compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)
 
 
 class BilstmCrfSoftword(BilstmCrf):
@@ -136,24 +139,32 @@ class BertBase(NerModel):
 
 
 class BertCe(BertBase):
-    """BERT -> dense -> masked softmax CE; argmax decode (model/bert_ce.py)."""
+    """BERT -> dense -> masked softmax CE; argmax decode (model/bert_ce.py).
+
+    compute_nbest runs the n-best op on log_softmax(logits) with zero
+    transitions (ops.token_nbest): tokens are independent, the partition
+    function is 1, so a path's logp is its score itself."""
 
     def __init__(self, params):
         super().__init__(params)
         self.logits = nn.Linear(self.hidden, params["label_size"])
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         logits = self.logits(self.encode(features))
         loss = None
         if "label_ids" in features:
             loss = self._loss(logits, features)
-        pred, conf = None, None
-        if compute_pred or compute_conf:
+        pred, conf, nbest = None, None, None
+        if compute_pred or compute_conf or compute_nbest > 0:
             pred = logits.argmax(-1) * features["mask"]
         if compute_conf:
             conf = ops.token_path_scores(logits, features["mask"], pred)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        if compute_nbest > 0:
+            nbest = ops.token_nbest(logits, features["mask"], compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)
 
     def _loss(self, logits, features):
         return ops.masked_cross_entropy(logits, features["label_ids"],
@@ -184,16 +195,19 @@ class BertCrf(BertBase):
         return self.encode(features)
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         logits = self.logits(self.encode_hidden(features))
         loss = None
         if "label_ids" in features:
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
-                                      compute_conf)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        pred, conf, nbest = self.crf.predict(
+            logits, features["mask"], compute_pred, compute_conf,
+            nbest=compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)
 
 
 class BertBilstmCrf(BertCrf):
@@ -248,7 +262,8 @@ class BertBilstmCrfBigram(NerModel):
         self.crf = CRF(params["label_size"])
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         if self.use_bert:
             emb = self.encoder(features["token_ids"], features["mask"])
         else:
@@ -264,9 +279,11 @@ class BertBilstmCrfBigram(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
-                                      compute_conf)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        pred, conf, nbest = self.crf.predict(
+            logits, features["mask"], compute_pred, compute_conf,
+            nbest=compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)
 
 
 class BertBilstmCrfSoftlexicon(BertCrf):

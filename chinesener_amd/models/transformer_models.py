@@ -35,7 +35,8 @@ class TransformerCrfBichar(NerModel):
         self.crf = CRF(params["label_size"])
 
     def forward(self, features, compute_pred: bool = False,
-                compute_conf: bool = False) -> ModelOutput:
+                compute_conf: bool = False,
+                compute_nbest: int = 0) -> ModelOutput:
         emb = torch.cat([self.char_emb(features["token_ids"]),
                          self.bichar_emb(features["bichar_ids"])], dim=-1)
         x = self.project(emb)
@@ -47,9 +48,11 @@ class TransformerCrfBichar(NerModel):
             loss = self.crf.neg_log_likelihood(
                 logits, features["label_ids"], features["mask"]) \
                 / features["token_ids"].shape[0]
-        pred, conf = self.crf.predict(logits, features["mask"], compute_pred,
-                                      compute_conf)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf)
+        pred, conf, nbest = self.crf.predict(
+            logits, features["mask"], compute_pred, compute_conf,
+            nbest=compute_nbest)
+        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
+                           nbest=nbest)
 
 
 class TransformerTenerCrfBichar(TransformerCrfBichar):

@@ -894,6 +894,80 @@ def crf_decode_scored(emissions, mask, transitions):
     return pred, span_a, span_b
 
 
+CRF_NBEST_MAX_K = 8
+
+
+def crf_nbest(emissions, mask, transitions, k):
+    """The k best tag paths of every row (list Viterbi, 1 <= k <= 8):
+    (paths long [B,k,L], scores f32 [B,k], logp f64 [B,k]), best first.
+    scores are unnormalised path scores; logp[b,r] = log P(path_r | x) is
+    crf_path_posterior's sequence probability (span_a[0] + span_b[len-1])
+    of each returned path. A row has min(k, T**len) paths: the ranks beyond
+    that get score and logp -inf and an all-zero path; positions >= len are
+    0. Order and tie rule: ops.reference.crf_nbest. Rank 0 is crf_viterbi's
+    path except under exact score ties, where the two may pick different
+    maximisers. No autograd.
+
+    Like crf_viterbi and crf_nll, the op reads a mask only as a length: the
+    real positions must be the first mask.sum(1) of a row. A mask with
+    holes or a leading gap (an MRC text_mask) decodes the wrong positions;
+    token_nbest handles such masks for heads without transitions."""
+    k = int(k)
+    if not 1 <= k <= CRF_NBEST_MAX_K:
+        raise ValueError(
+            f"crf_nbest: k must be in [1, {CRF_NBEST_MAX_K}], got {k}")
+    with torch.no_grad():
+        B, L, T = emissions.shape
+        if hip_enabled(emissions):
+            lens = mask.long().sum(1).to(torch.int32)
+            paths, scores = get_ext().crf_nbest(
+                emissions.detach().float().contiguous(), lens,
+                transitions.detach().float().contiguous(), k)
+            paths = paths.long()
+        else:
+            paths, scores = ref.crf_nbest(emissions.float(), mask,
+                                          transitions.float(), k)
+        # posterior of every returned path: B*k rows through the r9 op
+        flat_mask = mask.repeat_interleave(k, dim=0)
+        span_a, span_b = crf_path_posterior(
+            emissions.repeat_interleave(k, dim=0), flat_mask, transitions,
+            paths.reshape(B * k, L))
+        last = (flat_mask.long().sum(1) - 1).clamp(min=0)
+        logp = (span_a[:, 0] + span_b.gather(1, last[:, None]).squeeze(1)
+                ).reshape(B, k)
+        logp = torch.where(torch.isfinite(scores), logp,
+                           torch.full_like(logp, float("-inf")))
+        return paths, scores, logp
+
+
+def token_nbest(logits, mask, k):
+    """crf_nbest for heads that score tokens independently (softmax heads):
+    the same op on log_softmax(logits) with zero transitions. The partition
+    function of that chain is 1, so logp is the path score itself (up to
+    the posterior kernel's rounding).
+
+    Position-wise like token_path_scores: ``mask`` may select any positions
+    of a row (an MRC text_mask starts after the query). crf_nbest itself
+    needs the real positions first, so the selected positions are moved to
+    the front in order, decoded, and the paths moved back; paths are 0 at
+    every position outside the mask. Without transitions the order of the
+    positions does not enter the scores."""
+    with torch.no_grad():
+        logprob = torch.log_softmax(logits.detach().float(), dim=-1)
+        B, L, T = logprob.shape
+        m = mask.to(torch.bool)
+        # stable: selected positions first, each group in its own order
+        order = torch.argsort((~m).long(), dim=1, stable=True)        # [B,L]
+        front = logprob.gather(1, order[:, :, None].expand(B, L, T))
+        prefix = (torch.arange(L, device=mask.device)[None, :]
+                  < m.sum(1)[:, None]).long()
+        paths, scores, logp = crf_nbest(front, prefix,
+                                        logprob.new_zeros(T, T), k)
+        back = torch.zeros_like(paths).scatter_(
+            2, order[:, None, :].expand(B, int(k), L), paths)
+        return back, scores, logp
+
+
 def token_path_scores(logits, mask, pred):
     """The span_a/span_b pair for heads that score tokens independently
     (softmax heads): with cum the running sum of log p_t(pred_t) over the

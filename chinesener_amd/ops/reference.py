@@ -342,6 +342,67 @@ def crf_path_posterior(emissions: torch.Tensor, mask: torch.Tensor,
     return span_a, span_b
 
 
+def crf_nbest(emissions: torch.Tensor, mask: torch.Tensor,
+              transitions: torch.Tensor, k: int
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best tag paths of every row (list Viterbi):
+    (paths [B,k,L] long, scores [B,k]), best first, computed in the dtype of
+    ``emissions`` (pass ``.double()`` for fp64).
+
+    scores[b,r] is the unnormalised score of the r-th best path: its
+    emissions plus the transitions along it over the len = mask.sum(1) real
+    positions.
+
+    Order, which also settles exact ties: for tag j at step t the candidates
+    (delta[t-1][i][r] + trans[i][j]) over predecessor i and rank r are ranked
+    by value descending, then i ascending, then r ascending; the first k are
+    kept and emis[t][j] is added afterwards (the association order of
+    crf_decode and the Viterbi kernels). The final ranking over (j, r) is by
+    value descending, then j, then r. Both are a stable descending sort over
+    the tag-major flattening.
+
+    A row has min(k, T**len) paths: ranks beyond that, and every rank of a
+    row with len <= 0, get score -inf and an all-zero path. Positions >= len
+    are 0."""
+    B, L, T = emissions.shape
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"crf_nbest: k must be >= 1, got {k}")
+    em = emissions.detach()
+    tr = transitions.detach().to(em.dtype)
+    dev = em.device
+    lens = mask.long().sum(1)                                    # [B]
+    ninf = float("-inf")
+    delta = em.new_full((B, T, k), ninf)                         # [B,T,k]
+    delta[:, :, 0] = em[:, 0]
+    history = []
+    for t in range(1, L):
+        # [B, (i,r), j]: predecessor-major, so a stable sort breaks ties by
+        # i and then r
+        cand = (delta[:, :, :, None] + tr[None, :, None, :]).reshape(
+            B, T * k, T)
+        vals, idx = torch.sort(cand, dim=1, descending=True, stable=True)
+        nxt = vals[:, :k].transpose(1, 2) + em[:, t][:, :, None]
+        delta = torch.where((t < lens)[:, None, None], nxt, delta)
+        history.append(idx[:, :k])                               # [B,k,T]
+    fin, fidx = torch.sort(delta.reshape(B, T * k), dim=1, descending=True,
+                           stable=True)
+    scores = fin[:, :k]
+    cur_j, cur_r = fidx[:, :k] // k, fidx[:, :k] % k             # [B,k]
+    paths = torch.zeros(B, k, L, dtype=torch.long, device=dev)
+    bi = torch.arange(B, device=dev)[:, None]
+    for t in range(L - 1, 0, -1):
+        within = (t < lens)[:, None]
+        paths[:, :, t] = torch.where(within, cur_j, torch.zeros_like(cur_j))
+        code = history[t - 1][bi, cur_r, cur_j]                  # (i, r) at t-1
+        cur_j = torch.where(within, code // k, cur_j)
+        cur_r = torch.where(within, code % k, cur_r)
+    paths[:, :, 0] = cur_j
+    present = torch.isfinite(scores) & (lens > 0)[:, None]
+    scores = torch.where(present, scores, torch.full_like(scores, ninf))
+    return paths * present[:, :, None].long(), scores
+
+
 # ------------------------------------------------------------------ lstm
 def lstm_forward(x: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
                  b: torch.Tensor, lens: torch.Tensor, reverse: bool = False,

@@ -16,6 +16,11 @@ With ``confidence=True`` the same path also runs the CRF path-posterior
 kernel (token-softmax heads: a cumulative log-softmax) and the captured
 outputs are (pred_ids, span_a, span_b): log P(tokens s..e carry the
 decoded tags) = span_a[s] + span_b[e], see ops.crf_path_posterior.
+
+With ``nbest=K`` (1..8) it also runs the n-best CRF decode and the captured
+outputs gain (nbest_paths [B,K,L], nbest_scores [B,K], nbest_logp [B,K]),
+see ops.crf_nbest. The two switches are independent and combine; pred_ids
+is the Viterbi decode on every engine.
 """
 from __future__ import annotations
 
@@ -46,6 +51,45 @@ _DEFAULTABLE_KEYS = frozenset({
 })
 
 
+NBEST_MAX = 8
+_CONF_KEYS = ("span_a", "span_b")
+_NBEST_KEYS = ("nbest_paths", "nbest_scores", "nbest_logp")
+
+
+def _need_nbest(name: str, have: int, k: Optional[int]) -> int:
+    """The k a predict_nbest call gets, or the RuntimeError it deserves."""
+    if not have:
+        raise RuntimeError(
+            f"engine for '{name}' was built without nbest; predict_nbest "
+            "needs InferenceEngine(..., nbest=K)")
+    k = have if k is None else int(k)
+    if not 1 <= k <= have:
+        raise RuntimeError(
+            f"engine for '{name}' was built with nbest={have}; "
+            f"predict_nbest(k={k}) needs 1 <= k <= {have}")
+    return k
+
+
+def _nbest_view(full: Dict[str, np.ndarray], k: int, lo: int = 0,
+                hi: Optional[int] = None, scored: bool = False
+                ) -> Dict[str, np.ndarray]:
+    """Rows lo:hi of a full result as predict_nbest returns them."""
+    out = {"pred_ids": full["pred_ids"][lo:hi]}
+    for key in _NBEST_KEYS:
+        out[key] = full[key][lo:hi, :k]
+    if scored:
+        for key in _CONF_KEYS:
+            out[key] = full[key][lo:hi]
+    return out
+
+
+def _need_confidence(name: str, have: bool):
+    if not have:
+        raise RuntimeError(
+            f"engine for '{name}' was built without confidence=True;"
+            " predict_scored needs InferenceEngine(..., confidence=True)")
+
+
 class _CapturedGraph:
     def __init__(self, graph, static_in: Dict[str, torch.Tensor],
                  static_out: Tuple[torch.Tensor, ...]):
@@ -64,9 +108,17 @@ class InferenceEngine:
                  max_seq_len: Optional[int] = None,
                  use_graph: Optional[bool] = None,
                  device: Optional[str] = None,
-                 confidence: bool = False):
+                 confidence: bool = False,
+                 nbest: int = 0):
         self.name = name
         self.confidence = bool(confidence)
+        self.nbest = int(nbest)
+        if not 0 <= self.nbest <= NBEST_MAX:
+            raise ValueError(
+                f"nbest must be between 0 and {NBEST_MAX}, got {nbest}")
+        self.out_keys = (("pred_ids",)
+                         + (_CONF_KEYS if self.confidence else ())
+                         + (_NBEST_KEYS if self.nbest else ()))
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         self.model, self.params = load_exported(name, export_root,
                                                 device=self.device,
@@ -119,12 +171,19 @@ class InferenceEngine:
 
     def _forward(self, feats: Dict[str, torch.Tensor]
                  ) -> Tuple[torch.Tensor, ...]:
-        """(pred_ids,) or, on a confidence engine, (pred_ids, span_a,
-        span_b)."""
-        if not self.confidence:
+        """The tensors named by self.out_keys: pred_ids, then span_a and
+        span_b on a confidence engine, then the nbest triple on an nbest
+        engine."""
+        if not (self.confidence or self.nbest):
             return (self.model(feats, compute_pred=True).pred_ids,)
-        out = self.model(feats, compute_pred=True, compute_conf=True)
-        return (out.pred_ids,) + tuple(out.span_scores)
+        if not self.nbest:
+            out = self.model(feats, compute_pred=True, compute_conf=True)
+            return (out.pred_ids,) + tuple(out.span_scores)
+        out = self.model(feats, compute_pred=True,
+                         compute_conf=self.confidence,
+                         compute_nbest=self.nbest)
+        conf = tuple(out.span_scores) if self.confidence else ()
+        return (out.pred_ids,) + conf + tuple(out.nbest)
 
     @torch.no_grad()
     def _capture(self, batch: int) -> _CapturedGraph:
@@ -187,13 +246,35 @@ class InferenceEngine:
         strict BIO entity's, which would also need the entity to stop at
         e); eval.decode_prediction_scored turns it into per-entity
         confidences. Needs an engine built with confidence=True."""
-        if not self.confidence:
-            raise RuntimeError(
-                f"engine for '{self.name}' was built without confidence=True;"
-                " predict_scored needs InferenceEngine(..., confidence=True)")
+        _need_confidence(self.name, self.confidence)
+        full = self.predict_full(features)
+        return {k: full[k] for k in ("pred_ids",) + _CONF_KEYS}
+
+    @torch.no_grad()
+    def predict_nbest(self, features: Dict[str, np.ndarray],
+                      k: Optional[int] = None, scored: bool = False
+                      ) -> Dict[str, np.ndarray]:
+        """predict() plus the k best tag paths of every row, best first:
+        {"pred_ids" [B,L], "nbest_paths" [B,k,L], "nbest_scores" [B,k] f32,
+        "nbest_logp" [B,k] f64}; exp(nbest_logp) is the posterior of the
+        whole path. Ranks a row does not have hold -inf and a zero path.
+        pred_ids is what predict() returns; rank 0 equals it except under
+        exact score ties. k defaults to the engine's nbest and may not
+        exceed it. Needs an engine built with nbest=K. scored=True adds
+        predict_scored's span_a/span_b from the same replay (the engine
+        then needs confidence=True as well)."""
+        k = _need_nbest(self.name, self.nbest, k)
+        if scored:
+            _need_confidence(self.name, self.confidence)
+        return _nbest_view(self.predict_full(features), k, scored=scored)
+
+    @torch.no_grad()
+    def predict_full(self, features: Dict[str, np.ndarray]
+                     ) -> Dict[str, np.ndarray]:
+        """Everything this engine computes per request, by name
+        (self.out_keys)."""
         with self._lock:
-            pred, span_a, span_b = self._predict(features)
-        return {"pred_ids": pred, "span_a": span_a, "span_b": span_b}
+            return dict(zip(self.out_keys, self._predict(features)))
 
     def _predict(self, features: Dict[str, np.ndarray]
                  ) -> Tuple[np.ndarray, ...]:
@@ -271,6 +352,10 @@ class MicroBatcher:
     def confidence(self):
         return self.engine.confidence
 
+    @property
+    def nbest(self):
+        return self.engine.nbest
+
     def warmup(self, requests=None):
         return self.engine.warmup(requests)
 
@@ -288,15 +373,24 @@ class MicroBatcher:
         """Engine.predict_scored through the batcher. Scored and plain
         requests of one signature share a replay; each caller gets back
         what it asked for."""
-        if not self.engine.confidence:
-            raise RuntimeError(
-                f"engine for '{self.name}' was built without confidence=True;"
-                " predict_scored needs InferenceEngine(..., confidence=True)")
+        _need_confidence(self.name, self.engine.confidence)
         return self._submit(features, scored=True)
 
-    def _submit(self, features: Dict[str, np.ndarray], scored: bool):
+    def predict_nbest(self, features: Dict[str, np.ndarray],
+                      k: Optional[int] = None, scored: bool = False
+                      ) -> Dict[str, np.ndarray]:
+        """Engine.predict_nbest through the batcher. Plain, scored and
+        nbest requests of one signature share one replay of everything the
+        engine computes; each caller gets back what it asked for."""
+        k = _need_nbest(self.name, self.engine.nbest, k)
+        if scored:
+            _need_confidence(self.name, self.engine.confidence)
+        return self._submit(features, scored=scored, nbest=k)
+
+    def _submit(self, features: Dict[str, np.ndarray], scored: bool,
+                nbest: int = 0):
         ev = threading.Event()
-        slot: Dict[str, object] = {"scored": scored}
+        slot: Dict[str, object] = {"scored": scored, "nbest": nbest}
         with self._cv:
             self._queue.append((features, slot, ev))
             self._cv.notify()
@@ -363,15 +457,21 @@ class MicroBatcher:
                 merged = {k: np.concatenate(
                     [np.asarray(f[k]) for f, _, _ in batch])
                     for k in batch[0][0]}
-                if any(slot["scored"] for _, slot, _ in batch):
+                if any(slot["nbest"] for _, slot, _ in batch):
+                    full = self.engine.predict_full(merged)  # the superset
+                elif any(slot["scored"] for _, slot, _ in batch):
                     full = self.engine.predict_scored(merged)
                 else:
                     full = {"pred_ids": self.engine.predict(merged)}
                 i = 0
                 for f, slot, ev in batch:
                     n = int(np.asarray(f["token_ids"]).shape[0])
-                    if slot["scored"]:
-                        slot["out"] = {k: v[i:i + n] for k, v in full.items()}
+                    if slot["nbest"]:
+                        slot["out"] = _nbest_view(full, slot["nbest"], i,
+                                                  i + n, slot["scored"])
+                    elif slot["scored"]:
+                        slot["out"] = {k: full[k][i:i + n]
+                                       for k in ("pred_ids",) + _CONF_KEYS}
                     else:
                         slot["out"] = full["pred_ids"][i:i + n]
                     i += n
@@ -397,3 +497,6 @@ class FastPredict:
 
     def predict_scored(self, features):
         return self.engine.predict_scored(features)
+
+    def predict_nbest(self, features, k=None, scored=False):
+        return self.engine.predict_nbest(features, k, scored)

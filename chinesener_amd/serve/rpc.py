@@ -57,7 +57,10 @@ def make_predict_request(model_name: str, inputs: Dict[str, np.ndarray],
                          options: Dict[str, Any] | None = None) -> Dict:
     """``options={"confidence": True}`` asks for span_a/span_b next to
     pred_ids in the response's outputs (the server must run with
-    confidence enabled). Without options the request is unchanged."""
+    confidence enabled). ``options={"nbest": k}`` asks for the k best tag
+    paths: nbest_paths [B,k,L], nbest_scores [B,k], nbest_logp [B,k] (the
+    server must run with --nbest K, K >= k). The two combine. Without
+    options the request is unchanged."""
     req = {"model_spec": {"name": model_name, "version": version,
                           "signature_name": signature},
            "inputs": inputs}

@@ -50,14 +50,31 @@ class PredictionServicer:
             context.abort(grpc.StatusCode.NOT_FOUND,
                           f"model '{name}' not loaded "
                           f"(loaded: {sorted(self.engines)})")
-        scored = bool((req.get("options") or {}).get("confidence"))
+        options = req.get("options") or {}
+        scored = bool(options.get("confidence"))
         if scored and not engine.confidence:
             context.abort(grpc.StatusCode.FAILED_PRECONDITION,
                           f"model '{name}' is served without confidence; "
                           "start the server with --confidence")
         try:
+            k = int(options.get("nbest") or 0)
+        except (TypeError, ValueError):
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          f"option nbest must be an integer, got "
+                          f"{options.get('nbest')!r}")
+        if k < 0:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          f"option nbest must be >= 0, got {k}")
+        if k > engine.nbest:
+            context.abort(grpc.StatusCode.FAILED_PRECONDITION,
+                          f"model '{name}' is served with nbest="
+                          f"{engine.nbest}, the request asks for {k}; "
+                          f"start the server with --nbest {k} or more")
+        try:
             t0 = time.perf_counter()
-            if scored:
+            if k:
+                outputs = engine.predict_nbest(req["inputs"], k, scored)
+            elif scored:
                 outputs = engine.predict_scored(req["inputs"])
             else:
                 outputs = {"pred_ids": engine.predict(req["inputs"])}
@@ -88,11 +105,12 @@ def serve(model_names, export_root: str = EXPORT_DIR,
           port: int = rpc.DEFAULT_PORT, wait: bool = True,
           use_graph=None, batch_sizes=(1, 4, 8), max_workers: int = 4,
           batching: bool = True, window_ms: float = 0.3,
-          confidence: bool = False):
+          confidence: bool = False, nbest: int = 0):
     engines = {}
     for name in model_names:
         eng = InferenceEngine(name, export_root, batch_sizes=batch_sizes,
-                              use_graph=use_graph, confidence=confidence)
+                              use_graph=use_graph, confidence=confidence,
+                              nbest=nbest)
         warm = load_warmup(latest_version_dir(name, export_root))
         eng.warmup(warm)
         log.info("loaded %s (%d warmup requests replayed)", name, len(warm))
@@ -120,11 +138,15 @@ def main(argv=None):
     ap.add_argument("--confidence", action="store_true",
                     help="also compute span scores, for requests that ask "
                          "for entity confidences")
+    ap.add_argument("--nbest", type=int, default=0, metavar="K",
+                    help="also compute the K best tag paths (1..8), for "
+                         "requests with options={'nbest': k}, k <= K")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     serve(args.model.split(","), args.export_root, args.port,
           use_graph=False if args.no_graph else None,
-          batching=not args.no_batching, confidence=args.confidence)
+          batching=not args.no_batching, confidence=args.confidence,
+          nbest=args.nbest)
     return 0
 
 

@@ -65,6 +65,12 @@ std::vector<at::Tensor> crf_path_posterior(const at::Tensor&,
                                            const at::Tensor&,
                                            const at::Tensor&,
                                            const at::Tensor&);
+// crf_nbest.hip (T <= 64, L <= 512, k <= 8): the k best tag paths per row,
+// {paths i32 [B,k,L], scores f32 [B,k]}; absent ranks: -inf, zero path
+std::vector<at::Tensor> crf_nbest(const at::Tensor&, const at::Tensor&,
+                                  const at::Tensor&, int64_t);
+// {global backpointer route (0/1), waves per block, LDS bytes} of that launch
+std::vector<int64_t> crf_nbest_route(int64_t, int64_t, int64_t);
 // softlexicon.hip
 at::Tensor softlexicon_fwd(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&);
@@ -194,6 +200,10 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("crf_viterbi", &crf_viterbi);
   m.def("crf_path_posterior", &crf_path_posterior, py::arg("emissions"),
         py::arg("lens"), py::arg("transitions"), py::arg("path"));
+  m.def("crf_nbest", &crf_nbest, py::arg("emissions"), py::arg("lens"),
+        py::arg("transitions"), py::arg("k"));
+  m.def("crf_nbest_route", &crf_nbest_route, py::arg("seq_len"),
+        py::arg("label_size"), py::arg("k"));
   m.def("softlexicon_fwd", &softlexicon_fwd);
   m.def("softlexicon_bwd", &softlexicon_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);

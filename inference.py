@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from chinesener_amd.data.datasets import get_spec
 from chinesener_amd.data.preprocess import extract_prefix_surfix, get_instance
-from chinesener_amd.eval import decode_prediction_scored, extract_entity
+from chinesener_amd.eval import (decode_prediction_nbest,
+                                 decode_prediction_scored, extract_entity)
 from chinesener_amd.serve.client import PredictionClient, timer
 from chinesener_amd.serve import rpc
 
@@ -78,6 +79,25 @@ class InferHelper:
         return decode_prediction_scored(tokens, tags, out["span_a"][0],
                                         out["span_b"][0], offset=offset)
 
+    @timer
+    def infer_nbest(self, sentence: str, k: int):
+        """The k best taggings of the sentence as {"alternatives": [{"rank",
+        "prob", "entities"}], "entities": [{"type", "text", "start", "end",
+        "support"}]} (eval.decode_prediction_nbest); the server must run
+        with --nbest K, K >= k. support is the probability mass of the
+        alternatives that contain the entity exactly, a lower bound on its
+        posterior."""
+        feats = self.make_feature(sentence)
+        resp = self.client.predict(self.model_name, feats, self.version,
+                                   options={"nbest": int(k)})
+        out = resp["outputs"]
+        tokens = self.proc.tokenizer.tokenize(sentence)
+        offset = 1 if self.proc.is_bert else 0  # skip [CLS]
+        tag_paths = [[self.idx2tag.get(int(i), "O") for i in path]
+                     for path in out["nbest_paths"][0]]
+        return decode_prediction_nbest(tokens, tag_paths,
+                                       out["nbest_logp"][0], offset=offset)
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
@@ -90,10 +110,20 @@ def main(argv=None):
     ap.add_argument("--confidence", action="store_true",
                     help="print each entity with its confidence (server "
                          "started with --confidence)")
+    ap.add_argument("--nbest", type=int, default=0, metavar="K",
+                    help="print the K best taggings with their probabilities "
+                         "and each entity's support (server started with "
+                         "--nbest K or more); not together with --confidence")
     args = ap.parse_args(argv)
+    if args.nbest > 0 and args.confidence:
+        ap.error("--nbest and --confidence print different things; "
+                 "give one of them")
     logging.basicConfig(level=logging.INFO)
     helper = InferHelper(args.model, args.data, args.host, args.port)
     infer = helper.infer_scored if args.confidence else helper.infer
+    if args.nbest > 0:
+        def infer(text, k=args.nbest):
+            return helper.infer_nbest(text, k)
     if args.text:
         print(infer(args.text))
         return 0

@@ -1,19 +1,24 @@
-"""CRF kernel timing: crf_fwd (loss + grads in one pass), crf_viterbi and
-crf_path_posterior at B=64 over the tag counts either side of the
-narrow/wide boundary and at the serving shapes (B = 1, 8), next to
-ops.reference (fwd+bwd / decode) on the same GPU and the same inputs.
+"""CRF kernel timing: crf_fwd (loss + grads in one pass), crf_viterbi,
+crf_path_posterior and crf_nbest (k = 4, 8) at B=64 over the tag counts
+either side of the narrow/wide boundary and at the serving shapes (B = 1,
+8), next to ops.reference (fwd+bwd / decode) on the same GPU and the same
+inputs.
 crf_fwd and crf_path_posterior both get the Viterbi path as their tags:
 crf_fwd runs the same two scans plus the alpha table and both gradients, so
-it is the yardstick the posterior kernel must not exceed.
+it is the yardstick the posterior kernel must not exceed. crf_nbest is the
+kernel alone (no path posterior); its yardstick is crf_viterbi on the same
+inputs, and the last column is that ratio. (64, 512, 64) is the shape whose
+backpointers go through the global workspace.
 Correctness is covered by tests/test_gpu_kernels.py,
-tests/test_gpu_crf_wide.py and tests/test_gpu_crf_posterior.py; this times
+tests/test_gpu_crf_wide.py, tests/test_gpu_crf_posterior.py and
+tests/test_gpu_crf_nbest.py; this times
 the extension entry points only.
 
 Method: device events around N back-to-back calls, after warm-up; R such
 windows per shape; the table reports the median window and the min..max
 spread, in microseconds per call. A shape the extension refuses, or an op
 it does not have, prints n/a, so the same script runs on a commit without
-the wide kernels or without crf_path_posterior.
+the wide kernels, without crf_path_posterior or without crf_nbest.
 
     python scripts/bench_crf.py [--out table.md] [--no-ref]
 """
@@ -78,8 +83,9 @@ def main():
     torch.manual_seed(0)
 
     lines = ["| B | L | T | crf_fwd us | ref fwd+bwd us | crf_viterbi us | "
-             "ref decode us | crf_path_posterior us |",
-             "|---|---|---|---|---|---|---|---|"]
+             "ref decode us | crf_path_posterior us | crf_nbest k=4 us | "
+             "crf_nbest k=8 us | nbest/viterbi k=4, k=8 |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
     print(torch.cuda.get_device_name(0), flush=True)
     for B, L, T in SHAPES:
         em = torch.randn(B, L, T, device="cuda")
@@ -104,6 +110,16 @@ def main():
             post = try_windows(
                 lambda: ext.crf_path_posterior(em, lens, trans, tags32),
                 n, args.reps, 5)
+        nb = {4: None, 8: None}
+        if hasattr(ext, "crf_nbest"):
+            for k in nb:
+                nb[k] = try_windows(
+                    lambda: ext.crf_nbest(em, lens, trans, k), n, args.reps, 5)
+        ratio = "n/a"
+        if vit and nb[4] and nb[8]:
+            v = statistics.median(vit)
+            ratio = (f"{statistics.median(nb[4]) / v:.1f}x, "
+                     f"{statistics.median(nb[8]) / v:.1f}x")
         rfwd = rvit = None
         if not args.no_ref:
             em_g = em.clone().requires_grad_()
@@ -122,7 +138,8 @@ def main():
             rfwd = windows(ref_step, 2, 3, 1)
             rvit = windows(ref_dec, 2, 3, 1)
         row = (f"| {B} | {L} | {T} | {fmt(fwd)} | {fmt(rfwd)} | {fmt(vit)} | "
-               f"{fmt(rvit)} | {fmt(post)} |")
+               f"{fmt(rvit)} | {fmt(post)} | {fmt(nb[4])} | {fmt(nb[8])} | "
+               f"{ratio} |")
         print(row, flush=True)
         lines.append(row)
     if args.out:

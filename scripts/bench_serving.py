@@ -5,7 +5,10 @@ requests. Run on an MI355X box; prints one JSON line.
 
 --confidence builds the engines with confidence=True and times
 predict_scored; the difference to a run without it is what entity
-confidences cost a request. --no_concurrency skips the 8-client part."""
+confidences cost a request. --nbest K builds them with nbest=K and times
+predict_nbest (with --confidence as well: both from one replay); the
+difference to a run without it is what the K best paths cost a request.
+--no_concurrency skips the 8-client part."""
 from __future__ import annotations
 
 import argparse
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--seq_len", type=int, default=150)
     ap.add_argument("--confidence", action="store_true")
+    ap.add_argument("--nbest", type=int, default=0, metavar="K")
     ap.add_argument("--no_concurrency", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available()
@@ -49,8 +53,12 @@ def main():
     export_model(model, name, params, export_root="/tmp/serving_bench")
 
     conf_kw = {"confidence": True} if args.confidence else {}
+    if args.nbest:
+        conf_kw["nbest"] = args.nbest
 
     def call_of(target):
+        if args.nbest:
+            return lambda f: target.predict_nbest(f, scored=args.confidence)
         return target.predict_scored if args.confidence else target.predict
 
     results = {}
@@ -131,7 +139,7 @@ def main():
     print(json.dumps({
         "metric": "serving latency, bert_bilstm_crf PREDICT (BERT-12L + BiLSTM + Viterbi)",
         "seq_len": args.seq_len, "requests": args.requests,
-        "confidence": args.confidence,
+        "confidence": args.confidence, "nbest": args.nbest,
         "results": results,
         "speedup_b1": round(results["eager_b1"]["p50_ms"]
                             / results["graph_b1"]["p50_ms"], 2)}))
