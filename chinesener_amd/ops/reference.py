@@ -198,8 +198,95 @@ def tener_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if mask is not None:
         key_mask = mask[:, None, None, :].to(scores.dtype)
         scores = scores + (1.0 - key_mask) * NEG_INF
-    probs = torch.softmax(scores.float(), dim=-1).to(q.dtype)
+    # softmax in at least fp32; fp64 inputs stay fp64 (the fp64 oracle of
+    # the TENER edge tests)
+    acc = scores if scores.dtype == torch.float64 else scores.float()
+    probs = torch.softmax(acc, dim=-1).to(q.dtype)
     return torch.matmul(probs, v)
+
+
+def _bf16_rt(x: torch.Tensor) -> torch.Tensor:
+    """Round to bf16 and back: one bf16 store of the kernel."""
+    return x.to(torch.bfloat16).to(torch.float64)
+
+
+def tener_attention_model(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                          u: torch.Tensor, vb: torch.Tensor,
+                          rel: torch.Tensor, mask: Optional[torch.Tensor],
+                          dout: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                     torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Rounding model of csrc/tener.hip and its wrapper
+    ops.functional.tener_attention: fp64 arithmetic with a bf16 round-trip
+    wherever the kernel or the wrapper stores bf16. Shapes as in
+    tener_attention; dout [B,H,L,D] is the upstream gradient. Returns
+    (out, dq, dk, dv, du, dvb) in fp64; every value is bf16-exact.
+
+    Rounding points (file:line at the time of writing):
+      inputs   q, k, v, u, vb, rel, dout to bf16  (functional.py, the
+               .to(bfloat16) casts of the wrapper; exact for bf16 inputs)
+      qu, qv   bf16(q+u), bf16(q+vb): the wrapper's bf16 adds
+      BD       qv R^T rounded to bf16 before the gather, forward
+               tener.hip:99-100 and again in the backward's recompute
+               tener.hip:260-261
+      lse      stored fp32, tener.hip:167 (the only fp32 point modelled)
+      P        softmax rounded to bf16 before P V, tener.hip:159
+      out      bf16, tener.hip:187-188
+      delta    rowsum(dout * out) from the bf16 out and dout,
+               tener.hip:232-234 (fp32 sum, not rounded here)
+      P (bwd)  exp(s - lse) rounded to bf16, tener.hip:286-288
+      dS       P (dP - delta) rounded to bf16, tener.hip:345-346
+      dv       P^T dO to bf16, tener.hip:319-320
+      dk       dS^T qu to bf16, tener.hip:377-378
+      dqu      dS K to bf16, tener.hip:415-416
+      dqv      dBD R to bf16, tener.hip:453-454 (dBD is dS scattered,
+               no further rounding)
+      dq       bf16(dqu + dqv): autograd's bf16 accumulation of the two
+               uses of q in the wrapper
+      du, dvb  bf16 of the sum of dqu (dqv) over batch and rows: the
+               reduction autograd forms over the wrapper's broadcast
+    Not modelled: fp32 accumulation order inside the MFMAs, __expf,
+    __logf, __frcp_rn, and the fp32 add of the AC and BD terms.
+
+    Key columns at or beyond a row's length score -1e30 as in the kernel;
+    an item of length 0 therefore gets the kernel's uniform 1/Lpad rows
+    in the forward (Lpad = L rounded up to 32) and zero gradients."""
+    B, H, L, D = q.shape
+    r = _bf16_rt
+    q_, k_, v_, do = (r(t.detach().double()) for t in (q, k, v, dout))
+    u_, vb_, rel_ = (r(t.detach().double()) for t in (u, vb, rel))
+    dev = q.device
+    lens = (mask.long().sum(1) if mask is not None
+            else torch.full((B,), L, dtype=torch.long, device=dev))
+    lpad = ((L + 31) // 32) * 32
+    qu = r(q_ + u_[None, :, None, :])
+    qv = r(q_ + vb_[None, :, None, :])
+    ar = torch.arange(L, device=dev)
+    idx = ((ar[None, :] - ar[:, None]) + (L - 1)).expand(B, H, L, L)
+    valid = (ar[None, :] < lens[:, None])[:, None, None, :]        # [B,1,1,L]
+
+    bd_full = r(torch.matmul(qv, rel_.transpose(0, 1)))            # [B,H,L,2L]
+    s = torch.matmul(qu, k_.transpose(-1, -2)) + bd_full.gather(-1, idx)
+    s = torch.where(valid, s, torch.full_like(s, NEG_INF))
+    mx = s.max(-1, keepdim=True).values
+    e = torch.exp(s - mx)
+    # an empty item: every column, the Lpad - L padded ones too, counts 1
+    pad_cols = (lens == 0).double()[:, None, None, None] * (lpad - L)
+    denom = e.sum(-1, keepdim=True) + pad_cols
+    lse = (mx + torch.log(denom)).float().double()
+    out = r(torch.matmul(r(e / denom), v_))
+
+    delta = (do * out).sum(-1, keepdim=True)
+    p = r(torch.where(valid, torch.exp(s - lse), torch.zeros_like(s)))
+    dv = r(torch.matmul(p.transpose(-1, -2), do))
+    dp = torch.matmul(do, v_.transpose(-1, -2))
+    ds = r(p * (dp - delta))
+    dk = r(torch.matmul(ds.transpose(-1, -2), qu))
+    dqu = r(torch.matmul(ds, k_))
+    dbd = torch.zeros_like(bd_full).scatter(-1, idx, ds)
+    dqv = r(torch.matmul(dbd, rel_))
+    return (out, r(dqu + dqv), dk, dv, r(dqu.sum((0, 2))),
+            r(dqv.sum((0, 2))))
 
 
 def sinusoidal_table(length: int, dim: int, device=None,
@@ -476,8 +563,10 @@ def masked_cross_entropy(logits: torch.Tensor, labels: torch.Tensor,
                          mask: torch.Tensor) -> torch.Tensor:
     """Mean CE over real tokens (reference tools/loss.py:5-16)."""
     T = logits.shape[-1]
-    loss = F.cross_entropy(logits.reshape(-1, T).float(), labels.reshape(-1),
-                           reduction="none")
+    # at least fp32; fp64 logits stay fp64 (the fp64 oracle of the tests)
+    lg = logits.reshape(-1, T)
+    lg = lg if lg.dtype == torch.float64 else lg.float()
+    loss = F.cross_entropy(lg, labels.reshape(-1), reduction="none")
     m = mask.reshape(-1).to(loss.dtype)
     return (loss * m).sum() / m.sum().clamp(min=1.0)
 
