@@ -368,10 +368,44 @@ def linear_dropout_add_layernorm(x, weight, bias, residual, ln_w, ln_b,
 
 
 # ---------------------------------------------------- embedding gather
+def _embed3_bwd_torch(dy, token_ids, segment_ids, vs, ps, ts):
+    """Scatter/sum in torch ops (the work nn.Embedding's backward does):
+    the route for shapes outside the kernel's limits and for
+    CHINESENER_EMBED3_BWD=off."""
+    B, L, H = dy.shape
+    # fp32 scatter accumulation: thousands of bf16 adds per heavy row
+    # (PAD, segment 0) would otherwise lose mass to rounding
+    dyf = dy.reshape(-1, H).float()
+    dw = torch.zeros(vs, dtype=torch.float32, device=dy.device)
+    dw.index_add_(0, token_ids.reshape(-1), dyf)
+    dw[0].zero_()          # padding_idx=0 semantics (nn.Embedding)
+    dp = torch.zeros(ps, dtype=torch.float32, device=dy.device)
+    dp[:L] = dy.float().sum(0)
+    dt = torch.zeros(ts, dtype=torch.float32, device=dy.device)
+    dt.index_add_(0, segment_ids.reshape(-1), dyf)
+    return dw.to(dy.dtype), dp.to(dy.dtype), dt.to(dy.dtype)
+
+
+def _embed3_bwd_eligible(dy, vs, ts) -> bool:
+    """Inside the limits the extension states for embed3_bwd: token_type
+    rows kept in registers, rows (B*L) the index build ranks, and the range
+    of its 32-bit sort key id * rows + row."""
+    if os.environ.get("CHINESENER_EMBED3_BWD") == "off":
+        return False
+    _, seg_cap, max_rows, max_keys = get_ext().embed3_bwd_limits()
+    B, L, H = dy.shape
+    R = B * L
+    return (dy.dtype == torch.bfloat16 and H % 8 == 0
+            and 1 <= ts[0] <= seg_cap and 1 <= R <= max_rows
+            and vs[0] * R <= max_keys)
+
+
 class _Embed3Fn(torch.autograd.Function):
     """Fused word+position+token_type gather-sum: one
-    kernel instead of three gathers + two adds. Backward keeps the
-    standard scatter/sum torch ops (same work nn.Embedding does)."""
+    kernel instead of three gathers + two adds. Backward is the sorted
+    segment sum of csrc/embed.hip (no float atomics, no fp32 tables);
+    B*L up to 32768 rows with vocab * B*L <= 2^32, at most 8 token_type
+    rows, hidden % 8 == 0. Anything else takes _embed3_bwd_torch."""
 
     @staticmethod
     def forward(ctx, word_w, pos_w, tok_w, token_ids, segment_ids):
@@ -385,19 +419,14 @@ class _Embed3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         token_ids, segment_ids = ctx.saved_tensors
         (vs, ps, ts) = ctx.shapes
-        B, L, H = dy.shape
-        # fp32 scatter accumulation: thousands of bf16 adds per heavy row
-        # (PAD, segment 0) would otherwise lose mass to rounding
-        dyf = dy.reshape(-1, H).float()
-        dw = torch.zeros(vs, dtype=torch.float32, device=dy.device)
-        dw.index_add_(0, token_ids.reshape(-1), dyf)
-        dw[0].zero_()          # padding_idx=0 semantics (nn.Embedding)
-        dp = torch.zeros(ps, dtype=torch.float32, device=dy.device)
-        dp[:L] = dy.float().sum(0)
-        dt = torch.zeros(ts, dtype=torch.float32, device=dy.device)
-        dt.index_add_(0, segment_ids.reshape(-1), dyf)
-        return (dw.to(dy.dtype), dp.to(dy.dtype), dt.to(dy.dtype),
-                None, None)
+        if _embed3_bwd_eligible(dy, vs, ts):
+            dw, dp, dt = get_ext().embed3_bwd(
+                dy.contiguous(), token_ids.contiguous(),
+                segment_ids.contiguous(), vs[0], ps[0], ts[0])
+        else:
+            dw, dp, dt = _embed3_bwd_torch(dy, token_ids, segment_ids,
+                                           vs, ps, ts)
+        return dw, dp, dt, None, None
 
 
 def embed3(word_w, pos_w, tok_w, token_ids, segment_ids):

@@ -48,6 +48,9 @@ std::vector<at::Tensor> gemm_nn_dgelu(const at::Tensor&, const at::Tensor&,
 at::Tensor embed3_fwd(const at::Tensor&, const at::Tensor&,
                       const at::Tensor&, const at::Tensor&,
                       const at::Tensor&);
+std::vector<at::Tensor> embed3_bwd(const at::Tensor&, const at::Tensor&,
+                                   const at::Tensor&, long, long, long);
+std::vector<long> embed3_bwd_limits();
 // crf.hip
 std::vector<at::Tensor> crf_fwd(const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, const at::Tensor&);
@@ -196,6 +199,9 @@ PYBIND11_MODULE(_hip_ops, m) {
   m.def("gemm_nn_dgelu", &gemm_nn_dgelu, py::arg("a"), py::arg("b"),
         py::arg("u"), py::arg("bias"));
   m.def("embed3_fwd", &embed3_fwd);
+  m.def("embed3_bwd", &embed3_bwd, py::arg("dy"), py::arg("token_ids"),
+        py::arg("segment_ids"), py::arg("V"), py::arg("P"), py::arg("S"));
+  m.def("embed3_bwd_limits", &embed3_bwd_limits);
   m.def("crf_fwd", &crf_fwd);
   m.def("crf_viterbi", &crf_viterbi);
   m.def("crf_path_posterior", &crf_path_posterior, py::arg("emissions"),
