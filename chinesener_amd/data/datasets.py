@@ -17,7 +17,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -46,6 +46,9 @@ class DatasetSpec:
     n_test: int
     avg_len: int = 45
     scheme: str = "bio"     # 'bio' NER or 'bies' CWS
+    # tag string that marks an unannotated position in this dataset's tag
+    # files; set = the features carry allowed_tags (data/partial.py)
+    unknown_tag: Optional[str] = None
 
     @property
     def idx2tag(self) -> Dict[int, str]:
@@ -81,7 +84,20 @@ DATASETS: Dict[str, DatasetSpec] = {
     "people_daily_augment": DatasetSpec(
         "people_daily_augment", _bio_tagset(["LOC", "PER", "ORG"]), 150,
         ["LOC", "PER", "ORG"], 20865, 2318, 4636),
+    # virtual datasets: a partially annotated train split ('?' = unknown)
+    # over the base corpus's fully labelled valid/test/predict splits
+    "msra_partial": DatasetSpec(
+        "msra_partial", _bio_tagset(["LOC", "PER", "ORG"]), 150,
+        ["LOC", "PER", "ORG"], 42000, 3000, 3442, unknown_tag="?"),
+    "cluener_fine_partial": DatasetSpec(
+        "cluener_fine_partial", _bio_tagset(CLUENER_TYPES), 150,
+        list(CLUENER_TYPES), 10748, 1343, 1345, unknown_tag="?"),
 }
+
+# partial dataset -> the base corpus its other splits (and, with no files
+# present, its thinned-out synthetic train split) come from
+PARTIAL_BASE = {"msra_partial": "msra",
+                "cluener_fine_partial": "cluener_fine"}
 
 
 def get_spec(name: str) -> DatasetSpec:
@@ -128,9 +144,11 @@ def load_conll(data_dir: str, file_name: str) -> Tuple[Sentences, Tags]:
 
 
 def load_cluener_json(data_dir: str, file_name: str,
-                      mapping: Dict[str, str] | None = None) -> Tuple[Sentences, Tags]:
+                      mapping: Dict[str, str] | None = None,
+                      outside: str = "O") -> Tuple[Sentences, Tags]:
     """CLUENER jsonl {text, label:{type:{surface:[[s,e],...]}}} -> BIO
-    (reference data/cluener/preprocess.py:20-66)."""
+    (reference data/cluener/preprocess.py:20-66). `outside` is the tag of a
+    character no span covers."""
     mapping = mapping or {"address": "LOC", "name": "PER", "company": "ORG",
                           "government": "ORG", "organization": "ORG"}
     sentences, tags = [], []
@@ -140,7 +158,7 @@ def load_cluener_json(data_dir: str, file_name: str,
                 continue
             rec = json.loads(line)
             text = rec["text"]
-            labels = ["O"] * len(text)
+            labels = [outside] * len(text)
             for etype, surf2spans in rec.get("label", {}).items():
                 mapped = mapping.get(etype)
                 if mapped is None:
@@ -158,6 +176,8 @@ def load_cluener_json(data_dir: str, file_name: str,
 def load_data(name: str, data_dir: str, split: str) -> Tuple[Sentences, Tags]:
     """Dispatch on dataset layout; falls back to synthetic when files absent."""
     spec = get_spec(name)
+    if name in PARTIAL_BASE:
+        return _load_partial(name, data_dir, split)
     try:
         if name == "people_daily_augment":
             # train comes from train_augment.pkl (augment.py dump);
@@ -183,6 +203,34 @@ def load_data(name: str, data_dir: str, split: str) -> Tuple[Sentences, Tags]:
                           else f"{split}.txt")
     except FileNotFoundError:
         return synthetic_corpus(spec, split)
+
+
+def _load_partial(name: str, data_dir: str, split: str
+                  ) -> Tuple[Sentences, Tags]:
+    """Partial datasets: the train split is read from the dataset's own
+    directory in the base corpus's layout, with the unknown tag allowed in
+    the tag column (msra) or standing for every character outside the
+    marked spans (cluener json: only entities were marked);
+    valid/test/predict are the base corpus's, fully labelled, so evaluation
+    is untouched. With no train files present the
+    train split is the base synthetic corpus passed through
+    mask_annotations(entity_keep=0.5, o_keep=0.3)."""
+    base = PARTIAL_BASE[name]
+    suffix = name[len(base):]                       # "_partial"
+    base_dir = (data_dir[:-len(suffix)] if data_dir.endswith(suffix)
+                else data_dir)
+    if split != "train":
+        return load_data(base, base_dir, split)
+    try:
+        if base == "msra":
+            return load_sentence_tag_dirs(data_dir, "train")
+        return load_cluener_json(data_dir, "train.json",
+                                 {t: t for t in CLUENER_TYPES},
+                                 outside=get_spec(name).unknown_tag)
+    except FileNotFoundError:
+        from .partial import mask_annotations
+        sentences, tags = synthetic_corpus(get_spec(base), "train")
+        return sentences, mask_annotations(tags, entity_keep=0.5, o_keep=0.3)
 
 
 # ------------------------------------------------------- synthetic corpus

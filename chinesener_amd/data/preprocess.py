@@ -18,6 +18,7 @@ import numpy as np
 
 from . import word_enhance as we
 from .datasets import DatasetSpec, get_spec, load_data, synthetic_corpus
+from .partial import as_int64, open_bits
 from .tokenizer import (CharTokenizer, Vocab, WordpieceTokenizer, get_tokenizer,
                         tokenizer_type_from_model)
 from .word_enhance import Lexicon
@@ -46,10 +47,14 @@ class BasicProc:
     word_enhance: Optional[str] = None
 
     def __init__(self, tokenizer, max_seq_len: int, tag2idx: Dict[str, int],
-                 lexicon: Optional[Lexicon] = None):
+                 lexicon: Optional[Lexicon] = None,
+                 unknown_tag: Optional[str] = None):
         self.tokenizer = tokenizer
         self.max_seq_len = max_seq_len
         self.tag2idx = tag2idx
+        # partially annotated dataset (DatasetSpec.unknown_tag): this tag
+        # string marks an unannotated position
+        self.unknown_tag = unknown_tag
         self.idx2tag = {v: k for k, v in tag2idx.items()}
         self.lexicon = lexicon
         self.is_bert = isinstance(tokenizer, WordpieceTokenizer)
@@ -57,6 +62,11 @@ class BasicProc:
     # ---- shared online/offline feature builder (reference :176-187) ----
     def build_seq_feature(self, sentence: str,
                           labels: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
+        """With an `unknown_tag`, every sample also carries ``allowed_tags``
+        (int64 [L]): per position one bit per permitted tag id: ``1 << id``
+        at a known tag and at [CLS] / [SEP] / [PAD], ``partial.open_bits``
+        at an unknown one. ``label_ids`` then holds ``O`` at the unknown
+        positions as a placeholder only; the partial loss does not read it."""
         L = self.max_seq_len
         body = L - 2 if self.is_bert else L
         tokens = self.tokenizer.tokenize(sentence)[:body]
@@ -66,8 +76,12 @@ class BasicProc:
             labels = list(labels)[:body]
             assert len(labels) == n, (
                 f"token/label length mismatch {n} vs {len(labels)}")
+            known = [t != self.unknown_tag for t in labels]
+            if self.unknown_tag is not None:
+                labels = [t if k else "O" for t, k in zip(labels, known)]
             lab_ids = [self.tag2idx[t] for t in labels]
         else:
+            known = [True] * n
             lab_ids = [self.tag2idx.get("O", 0)] * n
 
         pad_tag = self.tag2idx["[PAD]"]
@@ -87,6 +101,16 @@ class BasicProc:
             "mask": np.asarray(mask, dtype=np.int32),
             "seq_len": np.int32(seq_len),
         }
+        if self.unknown_tag is not None:
+            free = as_int64(open_bits(self.tag2idx))
+            words = [as_int64(1 << t) for t in lab]
+            off = 1 if self.is_bert else 0
+            for i, k in enumerate(known):
+                if not k:
+                    words[off + i] = free
+            # int64, not uint64: the loader converts every integer array
+            # with a value-preserving cast, which would mangle bit 63
+            feat["allowed_tags"] = np.asarray(words, dtype=np.int64)
         self._add_enhance(feat, sentence[:body])
         return feat
 
@@ -162,13 +186,15 @@ _PROCS = {None: BasicProc, "softword": SoftwordProc, "ex_softword": ExSoftwordPr
 def get_instance(tokenizer_type: str, max_seq_len: int, tag2idx: Dict[str, int],
                  word_enhance: Optional[str] = None,
                  vocab: Optional[Vocab] = None,
-                 lexicon: Optional[Lexicon] = None) -> BasicProc:
+                 lexicon: Optional[Lexicon] = None,
+                 unknown_tag: Optional[str] = None) -> BasicProc:
     """Factory mirroring reference get_instance (base_preprocess.py:74-91)."""
     tokenizer = get_tokenizer(tokenizer_type, vocab=vocab)
     if word_enhance is not None and lexicon is None:
         lexicon = Lexicon.synthetic(tokenizer.vocab.itos)
     cls = _PROCS[word_enhance]
-    return cls(tokenizer, max_seq_len, tag2idx, lexicon)
+    return cls(tokenizer, max_seq_len, tag2idx, lexicon,
+               unknown_tag=unknown_tag)
 
 
 # ------------------------------------------------------------- cache API
@@ -184,7 +210,8 @@ def build_cache(name: str, data_dir: str, model_name: str, splits=("train", "val
     """Preprocess corpus splits to {cache_name}.npz + data_params.pkl."""
     spec = spec or get_spec(name)
     enhance, tok_type = extract_prefix_surfix(model_name)
-    proc = get_instance(tok_type, spec.max_seq_len, spec.tag2idx, enhance)
+    proc = get_instance(tok_type, spec.max_seq_len, spec.tag2idx, enhance,
+                        unknown_tag=spec.unknown_tag)
     os.makedirs(data_dir, exist_ok=True)
 
     n_train = 0

@@ -31,6 +31,16 @@ class NerModel(nn.Module):
         super().__init__()
         self.params = dict(params)
 
+    def reject_partial_labels(self, features) -> None:
+        """For the heads that cannot train on partial annotations: a batch
+        of a partially annotated dataset is an error, not a silent fall back
+        to its placeholder label_ids."""
+        if "allowed_tags" in features:
+            raise ValueError(
+                f"{type(self).__name__}: the batch carries 'allowed_tags' "
+                "(a partially annotated dataset), which only the single-task "
+                "CRF models train on")
+
     def forward(self, features: Dict[str, torch.Tensor],
                 compute_pred: bool = False,
                 compute_conf: bool = False,

@@ -114,6 +114,25 @@ class CRF(nn.Module):
         ll = ops.crf_nll(emissions.float(), tags, mask, self.transitions)
         return -ll.sum()
 
+    def partial_neg_log_likelihood(self, emissions, allowed, mask
+                                   ) -> torch.Tensor:
+        """Sum over the batch of -log p(the paths inside the allowed sets |
+        emissions): the partial-annotation loss. allowed is int64 [B,L],
+        one bit per permitted tag id (ops.crf_partial_nll)."""
+        ll = ops.crf_partial_nll(emissions.float(), allowed, mask,
+                                 self.transitions)
+        return -ll.sum()
+
+    def loss(self, emissions, features) -> torch.Tensor:
+        """The batch's summed training loss: the partial-annotation loss
+        when the features carry "allowed_tags" (a partially annotated
+        dataset), else neg_log_likelihood of "label_ids"."""
+        if "allowed_tags" in features:
+            return self.partial_neg_log_likelihood(
+                emissions, features["allowed_tags"], features["mask"])
+        return self.neg_log_likelihood(emissions, features["label_ids"],
+                                       features["mask"])
+
     def decode(self, emissions, mask) -> torch.Tensor:
         return ops.crf_viterbi(emissions.float(), mask, self.transitions)
 

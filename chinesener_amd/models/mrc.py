@@ -40,6 +40,7 @@ class MrcBio(NerModel):
         loss = None
         text_mask = features.get("text_mask", features["mask"])
         if "label_ids" in features:
+            self.reject_partial_labels(features)
             loss = ops.masked_cross_entropy(logits, features["label_ids"],
                                             text_mask)
         pred, conf, nbest = None, None, None

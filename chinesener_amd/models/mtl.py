@@ -122,6 +122,7 @@ class BertBilstmCrfMtl(NerModel):
         # per-task masked NLL: -ll per sample, masked by task membership
         # (reference sums (-ll * mask) * weight / batch_size, :38-63)
         from .. import ops
+        self.reject_partial_labels(features)
         labels = features["label_ids"]
         # other-task samples are masked out of each tower's loss; clamp their
         # (other-tagset) label ids so the gather stays in range

@@ -55,8 +55,7 @@ class BilstmCrf(NerModel):
         logits = self.logits(hidden)
         loss = None
         if "label_ids" in features:
-            loss = self.crf.neg_log_likelihood(
-                logits, features["label_ids"], features["mask"]) \
+            loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
         pred, conf, nbest = self.crf.predict(
             logits, features["mask"], compute_pred, compute_conf,
@@ -155,6 +154,7 @@ class BertCe(BertBase):
         logits = self.logits(self.encode(features))
         loss = None
         if "label_ids" in features:
+            self.reject_partial_labels(features)
             loss = self._loss(logits, features)
         pred, conf, nbest = None, None, None
         if compute_pred or compute_conf or compute_nbest > 0:
@@ -200,8 +200,7 @@ class BertCrf(BertBase):
         logits = self.logits(self.encode_hidden(features))
         loss = None
         if "label_ids" in features:
-            loss = self.crf.neg_log_likelihood(
-                logits, features["label_ids"], features["mask"]) \
+            loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
         pred, conf, nbest = self.crf.predict(
             logits, features["mask"], compute_pred, compute_conf,
@@ -276,8 +275,7 @@ class BertBilstmCrfBigram(NerModel):
         logits = self.logits(hidden)
         loss = None
         if "label_ids" in features:
-            loss = self.crf.neg_log_likelihood(
-                logits, features["label_ids"], features["mask"]) \
+            loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
         pred, conf, nbest = self.crf.predict(
             logits, features["mask"], compute_pred, compute_conf,

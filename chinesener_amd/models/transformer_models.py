@@ -45,8 +45,7 @@ class TransformerCrfBichar(NerModel):
         logits = self.logits(x)
         loss = None
         if "label_ids" in features:
-            loss = self.crf.neg_log_likelihood(
-                logits, features["label_ids"], features["mask"]) \
+            loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
         pred, conf, nbest = self.crf.predict(
             logits, features["mask"], compute_pred, compute_conf,

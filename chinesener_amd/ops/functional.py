@@ -888,6 +888,65 @@ def crf_nll(emissions, tags, mask, transitions):
     return ref.crf_log_likelihood(emissions, tags, mask, transitions)
 
 
+class _CrfPartialFn(torch.autograd.Function):
+    """Partial-annotation log-likelihood [B]; the kernel emits the marginal
+    differences in the same launch (csrc/crf_partial.hip)."""
+
+    @staticmethod
+    def forward(ctx, emissions, allowed, lens, transitions):
+        ll, demis, dtrans = get_ext().crf_partial_fwd(emissions, allowed, lens,
+                                                      transitions)
+        ctx.save_for_backward(demis, dtrans)
+        return ll
+
+    @staticmethod
+    def backward(ctx, dll):
+        demis, dtrans = ctx.saved_tensors
+        return (demis * dll[:, None, None],
+                None, None,
+                (dtrans * dll[:, None, None]).sum(0))
+
+
+def crf_partial_nll(emissions, allowed, mask, transitions):
+    """Per-sequence partial-annotation log-likelihood [B] (caller negates/
+    averages): log Z over the paths inside the allowed sets minus log Z.
+    allowed is int64 [B,L], bit j of a word = tag j allowed, bits >= T
+    ignored, no bit below T = all tags (ops.reference
+    .crf_partial_log_likelihood has the definition; allowed_from_tags builds
+    the words). Like crf_nll, the op reads the mask only as a length."""
+    if hip_enabled(emissions):
+        lens = mask.long().sum(1).to(torch.int32)
+        return _CrfPartialFn.apply(emissions.float().contiguous(),
+                                   allowed.to(torch.int64).contiguous(), lens,
+                                   transitions.float().contiguous())
+    return ref.crf_partial_log_likelihood(emissions, allowed, mask,
+                                          transitions)
+
+
+def _i64_word(bits: int) -> int:
+    """A 64-bit pattern as the signed value int64 holds it (bit 63 = sign)."""
+    bits &= (1 << 64) - 1
+    return bits - (1 << 64) if bits >= 1 << 63 else bits
+
+
+def allowed_from_tags(tags, known, open_bits):
+    """int64 allowed-tag words for crf_partial_nll: ``1 << tag`` where
+    `known`, `open_bits` elsewhere. tags: integer tensor of tag ids < 64;
+    known: bool tensor of the same shape; open_bits: a Python int bit
+    pattern (bit 63 may be set, as an unsigned or as a negative value). The
+    singletons come from a table, because ``1 << 63`` does not fit a signed
+    Python-to-int64 conversion."""
+    table = torch.tensor([_i64_word(1 << i) for i in range(64)],
+                         dtype=torch.int64, device=tags.device)
+    # checked on the host only: a GPU caller must not be made to synchronise
+    if (not tags.is_cuda and tags.numel()
+            and (int(tags.min()) < 0 or int(tags.max()) > 63)):
+        raise ValueError("allowed_from_tags: tag ids must be in [0, 64)")
+    words = table[tags.long()]
+    rest = torch.full_like(words, _i64_word(int(open_bits)))
+    return torch.where(known.to(torch.bool), words, rest)
+
+
 def crf_viterbi(emissions, mask, transitions):
     if hip_enabled(emissions):
         lens = mask.long().sum(1).to(torch.int32)

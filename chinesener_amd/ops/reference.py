@@ -336,6 +336,55 @@ def crf_log_likelihood(emissions: torch.Tensor, tags: torch.Tensor,
     return score - log_z
 
 
+def allowed_sets(allowed: torch.Tensor, num_tags: int) -> torch.Tensor:
+    """bool [..., T]: the allowed-tag set each int64 word of `allowed` stands
+    for. Bit j < T set = tag j allowed; bits >= T are ignored; a word with no
+    bit below T set means "nothing known" and stands for all T tags."""
+    shifts = torch.arange(num_tags, device=allowed.device)
+    # an arithmetic shift of a negative word still leaves bit j in bit 0
+    bits = ((allowed.long().unsqueeze(-1) >> shifts) & 1).bool()
+    return bits | ~bits.any(dim=-1, keepdim=True)
+
+
+def crf_partial_log_likelihood(emissions: torch.Tensor, allowed: torch.Tensor,
+                               mask: torch.Tensor, transitions: torch.Tensor,
+                               dtype: torch.dtype = torch.float32
+                               ) -> torch.Tensor:
+    """Partial-annotation (fuzzy) CRF log-likelihood [B]:
+
+        ll[b] = log sum_{y: y_t in S_t} exp score(y) - log sum_y exp score(y)
+
+    over t < n_b, where n_b = mask[b].sum() (the mask is read as a length,
+    as in every CRF op here) and S_t is the set allowed[b,t] encodes
+    (allowed_sets). ll <= 0; one tag per position is crf_log_likelihood; all
+    tags everywhere gives exactly 0. A row with n_b = 0 gives 0. Plain torch,
+    differentiable by autograd: d ll / d emissions = P_S(y_t=j) - P(y_t=j).
+
+    Transitions that leave an allowed set without a finite-score path
+    (-1e4-style hard constraints) give a finite but meaningless value."""
+    B, L, T = emissions.shape
+    e = emissions.to(dtype)
+    trans = transitions.to(dtype)
+    lens = mask.long().sum(1)
+    neg = torch.full((), -1e30, dtype=dtype, device=e.device)
+
+    def log_z(open_):                       # open_: bool [B,L,T]
+        alpha = torch.where(open_[:, 0], e[:, 0], neg)
+        for t in range(1, L):
+            nxt = torch.logsumexp(alpha[:, :, None] + trans[None], dim=1)
+            nxt = torch.where(open_[:, t], nxt + e[:, t], neg)
+            alpha = torch.where((t < lens)[:, None], nxt, alpha)
+        return torch.logsumexp(alpha, dim=1)
+
+    sets = allowed_sets(allowed, T)
+    ll = log_z(sets) - log_z(torch.ones_like(sets))
+    # a row with no closed tag inside its length is the free sum itself: 0,
+    # and (through where) exactly zero gradients, not two that nearly cancel
+    inside = torch.arange(L, device=e.device)[None, :] < lens[:, None]
+    constrained = (~sets.all(dim=-1) & inside).any(dim=1)
+    return torch.where(constrained, ll, torch.zeros_like(ll))
+
+
 def crf_decode(emissions: torch.Tensor, mask: torch.Tensor,
                transitions: torch.Tensor) -> torch.Tensor:
     """Viterbi decode -> [B,L] best tag ids (padded positions keep tag of

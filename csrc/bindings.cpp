@@ -74,6 +74,13 @@ std::vector<at::Tensor> crf_nbest(const at::Tensor&, const at::Tensor&,
                                   const at::Tensor&, int64_t);
 // {global backpointer route (0/1), waves per block, LDS bytes} of that launch
 std::vector<int64_t> crf_nbest_route(int64_t, int64_t, int64_t);
+// crf_partial.hip (T <= 64, L <= 512): partial-annotation CRF. allowed is one
+// int64 word of permitted tags per position; {ll, demis, dtrans} of
+// ll = log Z_allowed - log Z
+std::vector<at::Tensor> crf_partial_fwd(const at::Tensor&, const at::Tensor&,
+                                        const at::Tensor&, const at::Tensor&);
+// {pair route (1) or split (0), waves per block, LDS bytes} of that launch
+std::vector<int64_t> crf_partial_route(int64_t, int64_t);
 // softlexicon.hip
 at::Tensor softlexicon_fwd(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&);
@@ -210,6 +217,10 @@ PYBIND11_MODULE(_hip_ops, m) {
         py::arg("transitions"), py::arg("k"));
   m.def("crf_nbest_route", &crf_nbest_route, py::arg("seq_len"),
         py::arg("label_size"), py::arg("k"));
+  m.def("crf_partial_fwd", &crf_partial_fwd, py::arg("emissions"),
+        py::arg("allowed"), py::arg("lens"), py::arg("transitions"));
+  m.def("crf_partial_route", &crf_partial_route, py::arg("seq_len"),
+        py::arg("label_size"));
   m.def("softlexicon_fwd", &softlexicon_fwd);
   m.def("softlexicon_bwd", &softlexicon_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);
