@@ -89,3 +89,28 @@ def distant_tags(sentence: str, entity_dict: Dict[str, List[str]]) -> List[str]:
             out[j] = f"I-{typ}"
         i = end
     return out
+
+
+def complete_annotations(model, features):
+    """Pseudo-labels for self-training on a partially annotated dataset:
+    decode `features` (a batch that carries ``allowed_tags``) under its own
+    annotation, so every annotated position keeps its tag and the model
+    fills in the rest. Returns ``(pred_ids long [B,L], path_score f32 [B])``;
+    a row whose annotation admits no path under the model's transition
+    constraints has score -inf and a zero row. Needs a single-task CRF
+    model."""
+    import torch
+
+    if "allowed_tags" not in features:
+        raise KeyError("complete_annotations: the batch has no 'allowed_tags'")
+    feats = {k: v for k, v in features.items()
+             if k not in ("label_ids", "allowed_tags")}
+    feats["constraint_tags"] = features["allowed_tags"]
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            out = model(feats, constrained=True)
+    finally:
+        model.train(was_training)
+    return out.pred_ids, out.path_score

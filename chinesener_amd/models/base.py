@@ -22,6 +22,9 @@ class ModelOutput(NamedTuple):
     # (paths long [B,k,L], scores f32 [B,k], logp f64 [B,k]): the k best tag
     # paths, best first; filled only with compute_nbest=k > 0
     nbest: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
+    # f32 [B]: unnormalised score of pred_ids, -inf on a row whose constraints
+    # admit no path; filled only with constrained=True
+    path_score: Optional[torch.Tensor] = None
 
 
 class NerModel(nn.Module):
@@ -41,16 +44,30 @@ class NerModel(nn.Module):
                 "(a partially annotated dataset), which only the single-task "
                 "CRF models train on")
 
+    def reject_constrained(self, constrained: bool) -> None:
+        """For the heads without constrained decoding."""
+        if constrained:
+            raise ValueError(
+                f"{type(self).__name__}: constrained=True is only available "
+                "on the single-task CRF models")
+
     def forward(self, features: Dict[str, torch.Tensor],
                 compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
         """compute_conf=True implies decoding and also fills
         ModelOutput.span_scores (see ops.crf_path_posterior).
         compute_nbest=k > 0 implies decoding and also fills
         ModelOutput.nbest with the k best paths (see ops.crf_nbest).
         pred_ids stays the Viterbi decode; rank 0 of nbest equals it except
-        under exact score ties."""
+        under exact score ties.
+        constrained=True (single-task CRF models) decodes under
+        features["constraint_tags"], int64 [B,L] allowed-tag words with 0 =
+        nothing known, and the transitions CRF.constrain_transitions set:
+        pred_ids becomes that path and path_score its score. With
+        compute_conf the span scores are the unconstrained model's posterior
+        of the returned path. Not combinable with compute_nbest."""
         raise NotImplementedError
 
 

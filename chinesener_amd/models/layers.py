@@ -108,6 +108,23 @@ class CRF(nn.Module):
         # all-O basin before the encoder learns anything
         self.transitions = nn.Parameter(
             torch.empty(num_tags, num_tags).uniform_(-0.01, 0.01))
+        # allowed-transition words of decode_constrained (None = all): not
+        # persistent, so checkpoints and exports do not change
+        self.register_buffer("trans_allowed", None, persistent=False)
+
+    def constrain_transitions(self, words) -> None:
+        """Set (or with None clear) the allowed-transition words constrained
+        decoding uses: int64 [num_tags], bit j of word i = transition i -> j
+        allowed (data.constraints.bio_transition_words builds the BIO ones).
+        Free decoding, the losses and the posteriors are not affected."""
+        if words is not None:
+            words = torch.as_tensor(words, dtype=torch.int64).to(
+                self.transitions.device).reshape(-1)
+            if words.numel() != self.num_tags:
+                raise ValueError(
+                    f"constrain_transitions: {words.numel()} words for "
+                    f"{self.num_tags} tags")
+        self.trans_allowed = words
 
     def neg_log_likelihood(self, emissions, tags, mask) -> torch.Tensor:
         """Sum of -log p(tags | emissions) over the batch."""
@@ -153,12 +170,39 @@ class CRF(nn.Module):
         ties."""
         return ops.crf_nbest(emissions.float(), mask, self.transitions, k)
 
+    def decode_constrained(self, emissions, mask, allowed):
+        """(pred long [B,L], score f32 [B]): the best path inside the
+        allowed-tag words (int64 [B,L], the words of the partial-annotation
+        loss; 0 = nothing known) that uses only the transitions set with
+        constrain_transitions. score is that path's unnormalised score; a
+        row whose constraints admit no path gets -inf and a zero row
+        (ops.crf_viterbi_constrained)."""
+        return ops.crf_viterbi_constrained(emissions.float(), allowed, mask,
+                                           self.transitions,
+                                           self.trans_allowed)
+
     def predict(self, emissions, mask, compute_pred: bool,
-                compute_conf: bool, *, nbest: int = 0):
+                compute_conf: bool, *, nbest: int = 0, allowed=None):
         """The (pred, span_scores, nbest) triple a model's forward returns:
         pred is decode()'s (None unless anything is asked for), span_scores
         is filled with compute_conf, nbest is decode_nbest(..., nbest) or
-        None when nbest is 0."""
+        None when nbest is 0.
+
+        With `allowed` (int64 [B,L] words) the decode is decode_constrained
+        and a fourth item, its path score [B], is returned. span_scores are
+        then crf_path_posterior of the constrained path: the unconstrained
+        model's posterior of what was returned, not a posterior conditioned
+        on the constraints. N-best under constraints is not available."""
+        if allowed is not None:
+            if nbest > 0:
+                raise ValueError(
+                    "constrained decoding cannot be combined with n-best")
+            pred, score = self.decode_constrained(emissions, mask, allowed)
+            conf = None
+            if compute_conf:
+                conf = ops.crf_path_posterior(emissions.float(), mask,
+                                              self.transitions, pred)
+            return pred, conf, None, score
         if compute_conf:
             pred, conf = self.decode_scored(emissions, mask)
         else:
@@ -166,6 +210,29 @@ class CRF(nn.Module):
             pred, conf = (self.decode(emissions, mask) if want else None), None
         best = self.decode_nbest(emissions, mask, nbest) if nbest > 0 else None
         return pred, conf, best
+
+    def outputs(self, emissions, features, compute_pred: bool,
+                compute_conf: bool, compute_nbest: int = 0,
+                constrained: bool = False) -> dict:
+        """predict() as the ModelOutput fields of a single-task CRF model:
+        pred_ids, span_scores, nbest and path_score. constrained=True decodes
+        under features["constraint_tags"]."""
+        if not constrained:
+            pred, conf, best = self.predict(
+                emissions, features["mask"], compute_pred, compute_conf,
+                nbest=compute_nbest)
+            return dict(pred_ids=pred, span_scores=conf, nbest=best)
+        if compute_nbest > 0:
+            raise ValueError(
+                "constrained=True cannot be combined with compute_nbest > 0")
+        if "constraint_tags" not in features:
+            raise KeyError(
+                "constrained=True needs features['constraint_tags'] (int64 "
+                "[B,L] allowed-tag words, 0 = nothing known)")
+        pred, conf, _, score = self.predict(
+            emissions, features["mask"], True, compute_conf,
+            allowed=features["constraint_tags"])
+        return dict(pred_ids=pred, span_scores=conf, path_score=score)
 
 
 class TokenEmbedding(nn.Module):

@@ -33,7 +33,9 @@ class MrcBio(NerModel):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
+        self.reject_constrained(constrained)
         seq = self.bert(features["token_ids"], features["mask"],
                         features.get("segment_ids"))
         logits = self.logits(self.dropout(seq))

@@ -73,7 +73,9 @@ class BertBilstmCrfMtl(NerModel):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
+        self.reject_constrained(constrained)
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")
@@ -163,7 +165,9 @@ class BertBilstmCrfAdv(BertBilstmCrfMtl):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
+        self.reject_constrained(constrained)
         seq = self._shared(features)
         lens = _lens(features)
         task_ids = features.get("task_ids")

@@ -47,7 +47,8 @@ class BilstmCrf(NerModel):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
         lens = _lens(features)
         emb = self.emb_dropout(self.embedding(features["token_ids"]))
         emb = self._enhance(features, emb)
@@ -57,11 +58,9 @@ class BilstmCrf(NerModel):
         if "label_ids" in features:
             loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
-        pred, conf, nbest = self.crf.predict(
-            logits, features["mask"], compute_pred, compute_conf,
-            nbest=compute_nbest)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
-                           nbest=nbest)
+        return ModelOutput(loss, logits=logits, **self.crf.outputs(
+            logits, features, compute_pred, compute_conf, compute_nbest,
+            constrained))
 
 
 class BilstmCrfSoftword(BilstmCrf):
@@ -150,7 +149,9 @@ class BertCe(BertBase):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
+        self.reject_constrained(constrained)
         logits = self.logits(self.encode(features))
         loss = None
         if "label_ids" in features:
@@ -196,17 +197,16 @@ class BertCrf(BertBase):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
         logits = self.logits(self.encode_hidden(features))
         loss = None
         if "label_ids" in features:
             loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
-        pred, conf, nbest = self.crf.predict(
-            logits, features["mask"], compute_pred, compute_conf,
-            nbest=compute_nbest)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
-                           nbest=nbest)
+        return ModelOutput(loss, logits=logits, **self.crf.outputs(
+            logits, features, compute_pred, compute_conf, compute_nbest,
+            constrained))
 
 
 class BertBilstmCrf(BertCrf):
@@ -262,7 +262,8 @@ class BertBilstmCrfBigram(NerModel):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
         if self.use_bert:
             emb = self.encoder(features["token_ids"], features["mask"])
         else:
@@ -277,11 +278,9 @@ class BertBilstmCrfBigram(NerModel):
         if "label_ids" in features:
             loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
-        pred, conf, nbest = self.crf.predict(
-            logits, features["mask"], compute_pred, compute_conf,
-            nbest=compute_nbest)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
-                           nbest=nbest)
+        return ModelOutput(loss, logits=logits, **self.crf.outputs(
+            logits, features, compute_pred, compute_conf, compute_nbest,
+            constrained))
 
 
 class BertBilstmCrfSoftlexicon(BertCrf):

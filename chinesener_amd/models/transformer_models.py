@@ -36,7 +36,8 @@ class TransformerCrfBichar(NerModel):
 
     def forward(self, features, compute_pred: bool = False,
                 compute_conf: bool = False,
-                compute_nbest: int = 0) -> ModelOutput:
+                compute_nbest: int = 0,
+                constrained: bool = False) -> ModelOutput:
         emb = torch.cat([self.char_emb(features["token_ids"]),
                          self.bichar_emb(features["bichar_ids"])], dim=-1)
         x = self.project(emb)
@@ -47,11 +48,9 @@ class TransformerCrfBichar(NerModel):
         if "label_ids" in features:
             loss = self.crf.loss(logits, features) \
                 / features["token_ids"].shape[0]
-        pred, conf, nbest = self.crf.predict(
-            logits, features["mask"], compute_pred, compute_conf,
-            nbest=compute_nbest)
-        return ModelOutput(loss, pred, logits=logits, span_scores=conf,
-                           nbest=nbest)
+        return ModelOutput(loss, logits=logits, **self.crf.outputs(
+            logits, features, compute_pred, compute_conf, compute_nbest,
+            constrained))
 
 
 class TransformerTenerCrfBichar(TransformerCrfBichar):

@@ -59,7 +59,7 @@ from .functional import (  # noqa: E402,F401
     layernorm, linear, linear_attention_qkv, linear_dropout_add_layernorm,
     crf_nll, crf_partial_nll, allowed_from_tags,
     crf_viterbi, crf_path_posterior, crf_decode_scored, token_path_scores,
-    crf_nbest, token_nbest,
+    crf_nbest, token_nbest, crf_viterbi_constrained,
     bilstm, softlexicon_fuse, masked_cross_entropy, dice_loss,
     tener_attention,
 )

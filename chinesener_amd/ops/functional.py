@@ -956,6 +956,35 @@ def crf_viterbi(emissions, mask, transitions):
         return ref.crf_decode(emissions, mask, transitions)
 
 
+def crf_viterbi_constrained(emissions, allowed, mask, transitions,
+                            trans_allowed=None):
+    """Viterbi under constraints: (pred long [B,L], score f32 [B]).
+    allowed is int64 [B,L] (bit j of a word = tag j allowed at that position,
+    bits >= T ignored, no bit below T = all tags: the words of
+    crf_partial_nll); trans_allowed is int64 [T] (bit j of word i =
+    transition i -> j allowed, no "empty means all" rule) or None for all.
+    score is the unnormalised score of the returned path; a row without a
+    path (len 0 or infeasible constraints) gets -inf and an all-zero row.
+    ops.reference.crf_decode_constrained has the definition. Like every CRF
+    op here it reads the mask only as a length. No autograd."""
+    with torch.no_grad():
+        if hip_enabled(emissions):
+            T = emissions.shape[-1]
+            lens = mask.long().sum(1).to(torch.int32)
+            if trans_allowed is None:
+                trans_allowed = torch.full((T,), -1, dtype=torch.int64,
+                                           device=emissions.device)
+            pred, score = get_ext().crf_viterbi_constrained(
+                emissions.detach().float().contiguous(),
+                allowed.to(torch.int64).contiguous(), lens,
+                transitions.detach().float().contiguous(),
+                trans_allowed.to(device=emissions.device,
+                                 dtype=torch.int64).contiguous())
+            return pred.long(), score
+        return ref.crf_decode_constrained(emissions.float(), allowed, mask,
+                                          transitions.float(), trans_allowed)
+
+
 def crf_path_posterior(emissions, mask, transitions, path):
     """(span_a, span_b), fp64 [B,L]: log P(y_s..y_e = path_s..path_e | x) =
     span_a[s] + span_b[e] for 0 <= s <= e < len (ops.reference

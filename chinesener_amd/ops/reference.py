@@ -418,6 +418,72 @@ def crf_decode(emissions: torch.Tensor, mask: torch.Tensor,
     return out * (pos < lens[:, None]).long()
 
 
+def transition_sets(trans_allowed: Optional[torch.Tensor], num_tags: int,
+                    device=None) -> torch.Tensor:
+    """bool [T,T]: cell [i,j] = transition i -> j allowed, from one int64
+    word per source tag (bit j of word i). Bits >= T are ignored. Unlike the
+    position words there is no "empty means all" rule: a tag whose word has
+    no bit below T set is terminal. None = everything allowed."""
+    if trans_allowed is None:
+        return torch.ones(num_tags, num_tags, dtype=torch.bool, device=device)
+    shifts = torch.arange(num_tags, device=trans_allowed.device)
+    return ((trans_allowed.long().unsqueeze(-1) >> shifts) & 1).bool()
+
+
+def crf_decode_constrained(emissions: torch.Tensor, allowed: torch.Tensor,
+                           mask: torch.Tensor, transitions: torch.Tensor,
+                           trans_allowed: Optional[torch.Tensor] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Viterbi under constraints: (pred long [B,L], score [B]), the best tag
+    path over the len = mask.sum(1) real positions among the paths that stay
+    inside the sets `allowed` encodes (allowed_sets: int64 [B,L], bit j = tag
+    j allowed, bits >= T ignored, no bit below T = all tags) and use only
+    the transitions `trans_allowed` permits (transition_sets: int64 [T], bit
+    j of word i = i -> j allowed, None = all). Computed in the dtype of
+    ``emissions`` (pass ``.double()`` for fp64).
+
+    Arithmetic and tie rule are crf_decode's: delta[t][j] = max_i(delta[t-1]
+    [i] + trans[i][j]) + e[t][j], first maximum in index order per step and
+    for the final tag. Masking is a select: forbidden transitions are NEG =
+    -1e30 cells, and a tag that is closed at t or whose best predecessor
+    term is not above NEG/2 is reset to exactly NEG, so nothing accumulates
+    on NEG. Contract: real path scores stay above -1e29.
+
+    score is the returned path's unnormalised score. A row without a path
+    (len 0, or an infeasible constraint set) gets score -inf and an all-zero
+    pred row; positions >= len are 0."""
+    B, L, T = emissions.shape
+    e = emissions.detach()
+    dev = e.device
+    neg = torch.full((), -1e30, dtype=e.dtype, device=dev)
+    half = -0.5e30
+    tr = torch.where(transition_sets(trans_allowed, T, dev).to(dev),
+                     transitions.detach().to(e.dtype), neg)
+    sets = allowed_sets(allowed, T)                              # [B,L,T]
+    lens = mask.long().sum(1)                                    # [B]
+    delta = torch.where(sets[:, 0], e[:, 0], neg)                # [B,T]
+    history = []
+    for t in range(1, L):
+        best, idx = (delta[:, :, None] + tr[None]).max(dim=1)    # over i
+        nxt = torch.where(sets[:, t] & (best > half), best + e[:, t], neg)
+        delta = torch.where((t < lens)[:, None], nxt, delta)
+        history.append(idx)
+    score, cur = delta.max(dim=1)
+    feasible = (score > half) & (lens > 0)
+    out = torch.zeros(B, L, dtype=torch.long, device=dev)
+    out[:, L - 1] = cur
+    bi = torch.arange(B, device=dev)
+    for t in range(L - 2, -1, -1):
+        prev = history[t][bi, cur]          # transition t -> t+1 backpointers
+        cur = torch.where((t + 1) < lens, prev, cur)
+        out[:, t] = cur
+    pos = torch.arange(L, device=dev)[None, :]
+    keep = (pos < lens[:, None]) & feasible[:, None]
+    score = torch.where(feasible, score,
+                        torch.full_like(score, float("-inf")))
+    return out * keep.long(), score
+
+
 def crf_path_posterior(emissions: torch.Tensor, mask: torch.Tensor,
                        transitions: torch.Tensor, path: torch.Tensor,
                        dtype: torch.dtype = torch.float64

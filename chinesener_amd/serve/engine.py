@@ -21,6 +21,14 @@ With ``nbest=K`` (1..8) it also runs the n-best CRF decode and the captured
 outputs gain (nbest_paths [B,K,L], nbest_scores [B,K], nbest_logp [B,K]),
 see ops.crf_nbest. The two switches are independent and combine; pred_ids
 is the Viterbi decode on every engine.
+
+With ``constraints=True`` the decode is the constrained Viterbi kernel
+(ops.crf_viterbi_constrained): ``constraint_tags`` (int64 [batch, L]
+allowed-tag words, data.constraints builds them) becomes one more static
+input whose zero default means "nothing known", so hinted and plain requests
+replay the same graph, and the outputs gain path_score [B]. ``trans_allowed``
+(int64 [T], e.g. data.constraints.bio_transition_words) is applied once to
+the model's CRF. Not combinable with nbest.
 """
 from __future__ import annotations
 
@@ -39,7 +47,8 @@ log = logging.getLogger("chinesener_amd.serve")
 
 # feature dtypes the models consume (see data/preprocess.py feature build)
 _INT_KEYS = ("token_ids", "segment_ids", "mask", "label_ids", "task_ids",
-             "softword_ids", "softlexicon_ids", "bichar_ids")
+             "softword_ids", "softlexicon_ids", "bichar_ids",
+             "constraint_tags")
 
 # Captured-graph inputs a request may legitimately omit: an all-zeros
 # value is their semantic default (segment 0 = single-sentence BERT
@@ -50,6 +59,10 @@ _DEFAULTABLE_KEYS = frozenset({
     "softlexicon_ids", "softlexicon_weights", "bichar_ids",
 })
 
+
+# a constraints engine may also omit the allowed-tag words: all-zero words
+# say nothing about any position, which is free decoding
+_CONSTRAINT_KEY = "constraint_tags"
 
 NBEST_MAX = 8
 _CONF_KEYS = ("span_a", "span_b")
@@ -90,6 +103,22 @@ def _need_confidence(name: str, have: bool):
             " predict_scored needs InferenceEngine(..., confidence=True)")
 
 
+def _need_constraints(name: str, have: bool):
+    if not have:
+        raise RuntimeError(
+            f"engine for '{name}' was built without constraints=True; "
+            "constraint_tags and predict_constrained need "
+            "InferenceEngine(..., constraints=True)")
+
+
+def _constrained_view(full: Dict[str, np.ndarray], lo: int = 0,
+                      hi: Optional[int] = None, scored: bool = False
+                      ) -> Dict[str, np.ndarray]:
+    """Rows lo:hi of a full result as predict_constrained returns them."""
+    keys = ("pred_ids", "path_score") + (_CONF_KEYS if scored else ())
+    return {k: full[k][lo:hi] for k in keys}
+
+
 class _CapturedGraph:
     def __init__(self, graph, static_in: Dict[str, torch.Tensor],
                  static_out: Tuple[torch.Tensor, ...]):
@@ -109,16 +138,26 @@ class InferenceEngine:
                  use_graph: Optional[bool] = None,
                  device: Optional[str] = None,
                  confidence: bool = False,
-                 nbest: int = 0):
+                 nbest: int = 0,
+                 constraints: bool = False,
+                 trans_allowed=None):
         self.name = name
         self.confidence = bool(confidence)
         self.nbest = int(nbest)
+        self.constraints = bool(constraints)
         if not 0 <= self.nbest <= NBEST_MAX:
             raise ValueError(
                 f"nbest must be between 0 and {NBEST_MAX}, got {nbest}")
+        if self.constraints and self.nbest:
+            raise ValueError(
+                "constraints=True cannot be combined with nbest: n-best "
+                "under constraints is not available")
+        if trans_allowed is not None and not self.constraints:
+            raise ValueError("trans_allowed needs constraints=True")
         self.out_keys = (("pred_ids",)
                          + (_CONF_KEYS if self.confidence else ())
-                         + (_NBEST_KEYS if self.nbest else ()))
+                         + (_NBEST_KEYS if self.nbest else ())
+                         + (("path_score",) if self.constraints else ()))
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         self.model, self.params = load_exported(name, export_root,
                                                 device=self.device,
@@ -136,6 +175,15 @@ class InferenceEngine:
                           else self.device.startswith("cuda"))
         self._graphs: Dict[int, _CapturedGraph] = {}
         self._DEFAULTABLE = _DEFAULTABLE_KEYS
+        if self.constraints:
+            self._DEFAULTABLE = _DEFAULTABLE_KEYS | {_CONSTRAINT_KEY}
+            crf = getattr(self.model, "crf", None)
+            if crf is None:
+                raise ValueError(
+                    f"model '{name}' has no single-task CRF head; "
+                    "constraints=True needs one")
+            if trans_allowed is not None:
+                crf.constrain_transitions(trans_allowed)
         self.n_requests = 0
         self._lock = threading.Lock()
 
@@ -162,6 +210,8 @@ class InferenceEngine:
             feats["bichar_ids"] = torch.zeros(batch, L, dtype=torch.long)
         if "mtl" in name or "adv" in name:
             feats["task_ids"] = torch.ones(batch, L, dtype=torch.long)
+        if self.constraints:
+            feats[_CONSTRAINT_KEY] = torch.zeros(batch, L, dtype=torch.long)
         out = {}
         for k, v in feats.items():
             if v.is_floating_point() and self.bf16:
@@ -173,7 +223,12 @@ class InferenceEngine:
                  ) -> Tuple[torch.Tensor, ...]:
         """The tensors named by self.out_keys: pred_ids, then span_a and
         span_b on a confidence engine, then the nbest triple on an nbest
-        engine."""
+        engine or path_score on a constraints engine."""
+        if self.constraints:
+            out = self.model(feats, compute_pred=True,
+                             compute_conf=self.confidence, constrained=True)
+            conf = tuple(out.span_scores) if self.confidence else ()
+            return (out.pred_ids,) + conf + (out.path_score,)
         if not (self.confidence or self.nbest):
             return (self.model(feats, compute_pred=True).pred_ids,)
         if not self.nbest:
@@ -269,6 +324,22 @@ class InferenceEngine:
         return _nbest_view(self.predict_full(features), k, scored=scored)
 
     @torch.no_grad()
+    def predict_constrained(self, features: Dict[str, np.ndarray],
+                            scored: bool = False) -> Dict[str, np.ndarray]:
+        """Decode under features["constraint_tags"] (int64 [B,L] allowed-tag
+        words, 0 = nothing known; absent = all zero) and the engine's
+        trans_allowed: {"pred_ids" [B,L], "path_score" [B] f32}. path_score
+        is the unnormalised score of the returned path, -inf (and a zero
+        row) where the constraints admit no path. scored=True adds
+        span_a/span_b, the unconstrained model's posterior of the returned
+        path (the engine then needs confidence=True as well). Needs an
+        engine built with constraints=True."""
+        _need_constraints(self.name, self.constraints)
+        if scored:
+            _need_confidence(self.name, self.confidence)
+        return _constrained_view(self.predict_full(features), scored=scored)
+
+    @torch.no_grad()
     def predict_full(self, features: Dict[str, np.ndarray]
                      ) -> Dict[str, np.ndarray]:
         """Everything this engine computes per request, by name
@@ -279,6 +350,8 @@ class InferenceEngine:
     def _predict(self, features: Dict[str, np.ndarray]
                  ) -> Tuple[np.ndarray, ...]:
         self.n_requests += 1
+        if _CONSTRAINT_KEY in features:
+            _need_constraints(self.name, self.constraints)
         batch = features["token_ids"].shape[0]
         tensors = {}
         for k, v in features.items():
@@ -318,6 +391,8 @@ class InferenceEngine:
 
         # eager path (CPU, or batch larger than any bucket)
         dev = {k: t.to(self.device) for k, t in tensors.items()}
+        if self.constraints and _CONSTRAINT_KEY not in dev:
+            dev[_CONSTRAINT_KEY] = torch.zeros_like(dev["token_ids"])
         return tuple(o.cpu().numpy() for o in self._forward(dev))
 
 
@@ -356,6 +431,10 @@ class MicroBatcher:
     def nbest(self):
         return self.engine.nbest
 
+    @property
+    def constraints(self):
+        return self.engine.constraints
+
     def warmup(self, requests=None):
         return self.engine.warmup(requests)
 
@@ -387,10 +466,28 @@ class MicroBatcher:
             _need_confidence(self.name, self.engine.confidence)
         return self._submit(features, scored=scored, nbest=k)
 
+    def predict_constrained(self, features: Dict[str, np.ndarray],
+                            scored: bool = False) -> Dict[str, np.ndarray]:
+        """Engine.predict_constrained through the batcher. Hinted and plain
+        requests of one signature share a replay (a plain one rides along
+        with all-zero words); each caller gets back what it asked for."""
+        _need_constraints(self.name, self.engine.constraints)
+        if scored:
+            _need_confidence(self.name, self.engine.confidence)
+        return self._submit(features, scored=scored, constrained=True)
+
     def _submit(self, features: Dict[str, np.ndarray], scored: bool,
-                nbest: int = 0):
+                nbest: int = 0, constrained: bool = False):
+        if _CONSTRAINT_KEY in features:
+            _need_constraints(self.name, self.engine.constraints)
+        elif self.engine.constraints:
+            # before _sig is taken, so hinted and plain requests coalesce
+            features = dict(features)
+            features[_CONSTRAINT_KEY] = np.zeros(
+                np.asarray(features["token_ids"]).shape, dtype=np.int64)
         ev = threading.Event()
-        slot: Dict[str, object] = {"scored": scored, "nbest": nbest}
+        slot: Dict[str, object] = {"scored": scored, "nbest": nbest,
+                                   "constrained": constrained}
         with self._cv:
             self._queue.append((features, slot, ev))
             self._cv.notify()
@@ -457,7 +554,8 @@ class MicroBatcher:
                 merged = {k: np.concatenate(
                     [np.asarray(f[k]) for f, _, _ in batch])
                     for k in batch[0][0]}
-                if any(slot["nbest"] for _, slot, _ in batch):
+                if (self.engine.constraints
+                        or any(slot["nbest"] for _, slot, _ in batch)):
                     full = self.engine.predict_full(merged)  # the superset
                 elif any(slot["scored"] for _, slot, _ in batch):
                     full = self.engine.predict_scored(merged)
@@ -466,7 +564,10 @@ class MicroBatcher:
                 i = 0
                 for f, slot, ev in batch:
                     n = int(np.asarray(f["token_ids"]).shape[0])
-                    if slot["nbest"]:
+                    if slot["constrained"]:
+                        slot["out"] = _constrained_view(full, i, i + n,
+                                                        slot["scored"])
+                    elif slot["nbest"]:
                         slot["out"] = _nbest_view(full, slot["nbest"], i,
                                                   i + n, slot["scored"])
                     elif slot["scored"]:
@@ -500,3 +601,6 @@ class FastPredict:
 
     def predict_nbest(self, features, k=None, scored=False):
         return self.engine.predict_nbest(features, k, scored)
+
+    def predict_constrained(self, features, scored=False):
+        return self.engine.predict_constrained(features, scored)

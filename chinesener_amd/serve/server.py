@@ -71,8 +71,23 @@ class PredictionServicer:
                           f"{engine.nbest}, the request asks for {k}; "
                           f"start the server with --nbest {k} or more")
         try:
+            hinted = "constraint_tags" in req["inputs"]
+        except Exception as e:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          f"malformed request: {e}")
+        if hinted and not getattr(engine, "constraints", False):
+            context.abort(grpc.StatusCode.FAILED_PRECONDITION,
+                          f"model '{name}' is served without constraints; "
+                          "start the server with --constraints")
+        if hinted and k:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                          "constraint_tags cannot be combined with option "
+                          "nbest")
+        try:
             t0 = time.perf_counter()
-            if k:
+            if hinted:
+                outputs = engine.predict_constrained(req["inputs"], scored)
+            elif k:
                 outputs = engine.predict_nbest(req["inputs"], k, scored)
             elif scored:
                 outputs = engine.predict_scored(req["inputs"])
@@ -105,12 +120,14 @@ def serve(model_names, export_root: str = EXPORT_DIR,
           port: int = rpc.DEFAULT_PORT, wait: bool = True,
           use_graph=None, batch_sizes=(1, 4, 8), max_workers: int = 4,
           batching: bool = True, window_ms: float = 0.3,
-          confidence: bool = False, nbest: int = 0):
+          confidence: bool = False, nbest: int = 0,
+          constraints: bool = False, trans_allowed=None):
     engines = {}
     for name in model_names:
         eng = InferenceEngine(name, export_root, batch_sizes=batch_sizes,
                               use_graph=use_graph, confidence=confidence,
-                              nbest=nbest)
+                              nbest=nbest, constraints=constraints,
+                              trans_allowed=trans_allowed)
         warm = load_warmup(latest_version_dir(name, export_root))
         eng.warmup(warm)
         log.info("loaded %s (%d warmup requests replayed)", name, len(warm))
@@ -141,12 +158,30 @@ def main(argv=None):
     ap.add_argument("--nbest", type=int, default=0, metavar="K",
                     help="also compute the K best tag paths (1..8), for "
                          "requests with options={'nbest': k}, k <= K")
+    ap.add_argument("--constraints", action="store_true",
+                    help="decode under the allowed-tag words a request "
+                         "carries as inputs['constraint_tags'] (answered "
+                         "with pred_ids and path_score); not with --nbest")
+    ap.add_argument("--structure", choices=["bio"], default=None,
+                    help="with --constraints: allow only well-formed BIO "
+                         "transitions; needs --data for the tag map")
+    ap.add_argument("--data", default=None, metavar="NAME",
+                    help="dataset whose tag map --structure uses (the "
+                         "export carries none)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
+    trans_allowed = None
+    if args.structure:
+        if not (args.constraints and args.data):
+            ap.error("--structure needs --constraints and --data NAME")
+        from ..data.constraints import bio_transition_words
+        from ..data.datasets import get_spec
+        trans_allowed = bio_transition_words(get_spec(args.data).tag2idx)
     serve(args.model.split(","), args.export_root, args.port,
           use_graph=False if args.no_graph else None,
           batching=not args.no_batching, confidence=args.confidence,
-          nbest=args.nbest)
+          nbest=args.nbest, constraints=args.constraints,
+          trans_allowed=trans_allowed)
     return 0
 
 

@@ -81,6 +81,14 @@ std::vector<at::Tensor> crf_partial_fwd(const at::Tensor&, const at::Tensor&,
                                         const at::Tensor&, const at::Tensor&);
 // {pair route (1) or split (0), waves per block, LDS bytes} of that launch
 std::vector<int64_t> crf_partial_route(int64_t, int64_t);
+// crf_constrained.hip (T <= 64, L <= 512): Viterbi under per-position
+// allowed-tag words and per-tag allowed-transition words; {pred i32 [B,L],
+// score f32 [B]}, rows without a path: -inf and a zero row
+std::vector<at::Tensor> crf_viterbi_constrained(const at::Tensor&,
+                                                const at::Tensor&,
+                                                const at::Tensor&,
+                                                const at::Tensor&,
+                                                const at::Tensor&);
 // softlexicon.hip
 at::Tensor softlexicon_fwd(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&);
@@ -221,6 +229,9 @@ PYBIND11_MODULE(_hip_ops, m) {
         py::arg("allowed"), py::arg("lens"), py::arg("transitions"));
   m.def("crf_partial_route", &crf_partial_route, py::arg("seq_len"),
         py::arg("label_size"));
+  m.def("crf_viterbi_constrained", &crf_viterbi_constrained,
+        py::arg("emissions"), py::arg("allowed"), py::arg("lens"),
+        py::arg("transitions"), py::arg("trans_allowed"));
   m.def("softlexicon_fwd", &softlexicon_fwd);
   m.def("softlexicon_bwd", &softlexicon_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);

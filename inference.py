@@ -20,6 +20,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from chinesener_amd.data.constraints import forbid_types, span_words
 from chinesener_amd.data.datasets import get_spec
 from chinesener_amd.data.preprocess import extract_prefix_surfix, get_instance
 from chinesener_amd.eval import (decode_prediction_nbest,
@@ -36,6 +37,7 @@ class InferHelper:
         spec = get_spec(data)
         self.max_seq_len = max_seq_len or spec.max_seq_len
         self.idx2tag = spec.idx2tag
+        self.tag2idx = spec.tag2idx
         enhance, tok_type = extract_prefix_surfix(model_name)
         self.proc = get_instance(tok_type, self.max_seq_len, spec.tag2idx,
                                  enhance)
@@ -98,6 +100,53 @@ class InferHelper:
         return decode_prediction_nbest(tokens, tag_paths,
                                        out["nbest_logp"][0], offset=offset)
 
+    def constraint_words(self, n_tokens: int, spans=(), forbid=()
+                         ) -> np.ndarray:
+        """int64 [1, max_seq_len] allowed-tag words of a sentence of
+        n_tokens tokens: span_words for the hints, forbid_types for the
+        rest of the tokens; [CLS], [SEP] and the padding stay 0 (nothing
+        known)."""
+        offset = 1 if self.proc.is_bert else 0
+        n = min(n_tokens, self.max_seq_len - 2 * offset)
+        inner = span_words(spans, n, self.tag2idx)
+        if forbid:
+            inner = forbid_types(inner, forbid, self.tag2idx)
+        words = np.zeros((1, self.max_seq_len), dtype=np.int64)
+        words[0, offset:offset + n] = inner
+        return words
+
+    @timer
+    def infer_constrained(self, sentence: str, spans=(), forbid=()):
+        """infer() under what the caller knows: `spans` are (type, start,
+        end) hints in token positions, end exclusive, that the tagging must
+        contain; `forbid` are entity types it must not contain outside the
+        hints. Returns {"entities": infer()'s dict, "feasible": bool,
+        "path_score": float}; feasible is False (and entities empty) when no
+        tagging satisfies the constraints. The server must run with
+        --constraints."""
+        feats = self.make_feature(sentence)
+        tokens = self.proc.tokenizer.tokenize(sentence)
+        feats["constraint_tags"] = self.constraint_words(len(tokens), spans,
+                                                         forbid)
+        resp = self.client.predict(self.model_name, feats, self.version)
+        out = resp["outputs"]
+        score = float(out["path_score"][0])
+        offset = 1 if self.proc.is_bert else 0  # skip [CLS]
+        tags = [self.idx2tag.get(int(i), "O")
+                for i in out["pred_ids"][0][offset:offset + len(tokens)]]
+        feasible = score > float("-inf")
+        return {"entities": extract_entity(tokens, tags) if feasible else {},
+                "feasible": feasible, "path_score": score}
+
+
+def _parse_hint(text: str):
+    try:
+        typ, start, end = text.rsplit(":", 2)
+        return typ, int(start), int(end)
+    except ValueError:
+        raise argparse.ArgumentTypeError(
+            f"hint must be TYPE:START:END, got {text!r}")
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
@@ -114,7 +163,20 @@ def main(argv=None):
                     help="print the K best taggings with their probabilities "
                          "and each entity's support (server started with "
                          "--nbest K or more); not together with --confidence")
+    ap.add_argument("--hint", action="append", default=[], type=_parse_hint,
+                    metavar="TYPE:START:END",
+                    help="an entity the tagging must contain, in token "
+                         "positions with END exclusive; repeatable (server "
+                         "started with --constraints)")
+    ap.add_argument("--forbid", action="append", default=[], metavar="TYPE",
+                    help="an entity type the tagging must not contain; "
+                         "repeatable (server started with --constraints)")
     args = ap.parse_args(argv)
+    constrained = bool(args.hint or args.forbid)
+    if constrained and args.nbest > 0:
+        ap.error("--hint/--forbid cannot be combined with --nbest")
+    if constrained and args.confidence:
+        ap.error("--hint/--forbid cannot be combined with --confidence")
     if args.nbest > 0 and args.confidence:
         ap.error("--nbest and --confidence print different things; "
                  "give one of them")
@@ -124,6 +186,9 @@ def main(argv=None):
     if args.nbest > 0:
         def infer(text, k=args.nbest):
             return helper.infer_nbest(text, k)
+    if constrained:
+        def infer(text):
+            return helper.infer_constrained(text, args.hint, args.forbid)
     if args.text:
         print(infer(args.text))
         return 0

@@ -8,6 +8,10 @@ predict_scored; the difference to a run without it is what entity
 confidences cost a request. --nbest K builds them with nbest=K and times
 predict_nbest (with --confidence as well: both from one replay); the
 difference to a run without it is what the K best paths cost a request.
+--constraints builds them with constraints=True and times
+predict_constrained on requests without hints (zero words: the captured
+graph is the same for hinted requests); the difference to a run without it
+is what the constrained decode costs a request.
 --no_concurrency skips the 8-client part."""
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--seq_len", type=int, default=150)
     ap.add_argument("--confidence", action="store_true")
     ap.add_argument("--nbest", type=int, default=0, metavar="K")
+    ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--no_concurrency", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available()
@@ -56,7 +61,13 @@ def main():
     if args.nbest:
         conf_kw["nbest"] = args.nbest
 
+    if args.constraints:
+        conf_kw["constraints"] = True
+
     def call_of(target):
+        if args.constraints:
+            return lambda f: target.predict_constrained(
+                f, scored=args.confidence)
         if args.nbest:
             return lambda f: target.predict_nbest(f, scored=args.confidence)
         return target.predict_scored if args.confidence else target.predict
@@ -140,6 +151,7 @@ def main():
         "metric": "serving latency, bert_bilstm_crf PREDICT (BERT-12L + BiLSTM + Viterbi)",
         "seq_len": args.seq_len, "requests": args.requests,
         "confidence": args.confidence, "nbest": args.nbest,
+        "constraints": args.constraints,
         "results": results,
         "speedup_b1": round(results["eager_b1"]["p50_ms"]
                             / results["graph_b1"]["p50_ms"], 2)}))
