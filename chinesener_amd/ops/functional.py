@@ -859,6 +859,20 @@ def tener_attention(q, k, v, u, vb, rel, mask: Optional[torch.Tensor] = None):
 
 
 # ------------------------------------------------------------------ crf
+def _crf_grad_scale(demis, dtrans, dll):
+    """Chain rule of both CRF losses: (demis * dll[b], sum_b dtrans[b] *
+    dll[b]). One launch on the HIP path (csrc/crf_pair.hip), into new
+    tensors: the saved ones must survive a second backward."""
+    if hip_enabled(demis):
+        # dll as it comes (a summed loss hands an expanded scalar): the
+        # kernel reads it through its stride, no copy
+        d_em, d_tr = get_ext().crf_grad_scale(demis, dtrans,
+                                              dll.to(torch.float32))
+        return d_em, d_tr
+    return (demis * dll[:, None, None],
+            (dtrans * dll[:, None, None]).sum(0))
+
+
 class _CrfNllFn(torch.autograd.Function):
     """log-likelihood [B]; kernel computes grads (marginals) in the same
     forward-backward pass."""
@@ -873,9 +887,8 @@ class _CrfNllFn(torch.autograd.Function):
     def backward(ctx, dll):
         demis, dtrans = ctx.saved_tensors
         # d(ll_b)/d(emissions) stored as +(gold - expected); chain rule with dll.
-        return (demis * dll[:, None, None],
-                None, None,
-                (dtrans * dll[:, None, None]).sum(0))
+        d_em, d_tr = _crf_grad_scale(demis, dtrans, dll)
+        return d_em, None, None, d_tr
 
 
 def crf_nll(emissions, tags, mask, transitions):
@@ -902,9 +915,8 @@ class _CrfPartialFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dll):
         demis, dtrans = ctx.saved_tensors
-        return (demis * dll[:, None, None],
-                None, None,
-                (dtrans * dll[:, None, None]).sum(0))
+        d_em, d_tr = _crf_grad_scale(demis, dtrans, dll)
+        return d_em, None, None, d_tr
 
 
 def crf_partial_nll(emissions, allowed, mask, transitions):

@@ -56,8 +56,18 @@ std::vector<at::Tensor> crf_fwd(const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, const at::Tensor&);
 at::Tensor crf_viterbi(const at::Tensor&, const at::Tensor&,
                        const at::Tensor&);
+// crf_pair.hip (T <= 64, both scan tables of a row in LDS): the loss kernel
+// crf_fwd routes to; seqs_per_block 0 = the route's choice, 1 / 2 force it
+std::vector<at::Tensor> crf_pair_fwd(const at::Tensor&, const at::Tensor&,
+                                     const at::Tensor&, const at::Tensor&,
+                                     int64_t);
+// {pair kernel (1) or crf_wide.hip (0), waves per block, LDS bytes}
+std::vector<int64_t> crf_fwd_route(int64_t, int64_t);
+// {demis * dll[b], sum_b dtrans[b] * dll[b]} in one launch, new tensors
+std::vector<at::Tensor> crf_grad_scale(const at::Tensor&, const at::Tensor&,
+                                       const at::Tensor&);
 // crf_wide.hip (T <= 64, L <= 512): reached through crf_fwd / crf_viterbi,
-// which route to it every shape the narrow kernels cannot launch
+// which route to it every shape their other kernels cannot launch
 std::vector<at::Tensor> crf_wide_fwd(const at::Tensor&, const at::Tensor&,
                                      const at::Tensor&, const at::Tensor&);
 at::Tensor crf_wide_viterbi(const at::Tensor&, const at::Tensor&,
@@ -218,6 +228,13 @@ PYBIND11_MODULE(_hip_ops, m) {
         py::arg("segment_ids"), py::arg("V"), py::arg("P"), py::arg("S"));
   m.def("embed3_bwd_limits", &embed3_bwd_limits);
   m.def("crf_fwd", &crf_fwd);
+  m.def("crf_pair_fwd", &crf_pair_fwd, py::arg("emissions"), py::arg("tags"),
+        py::arg("lens"), py::arg("transitions"),
+        py::arg("seqs_per_block") = 0);
+  m.def("crf_fwd_route", &crf_fwd_route, py::arg("seq_len"),
+        py::arg("label_size"));
+  m.def("crf_grad_scale", &crf_grad_scale, py::arg("demis"),
+        py::arg("dtrans"), py::arg("dll"));
   m.def("crf_viterbi", &crf_viterbi);
   m.def("crf_path_posterior", &crf_path_posterior, py::arg("emissions"),
         py::arg("lens"), py::arg("transitions"), py::arg("path"));

@@ -82,10 +82,10 @@ def main():
     ext = ops.get_ext()
     torch.manual_seed(0)
 
-    lines = ["| B | L | T | crf_fwd us | ref fwd+bwd us | crf_viterbi us | "
+    lines = ["| B | L | T | crf_fwd route | crf_fwd us | ref fwd+bwd us | crf_viterbi us | "
              "ref decode us | crf_path_posterior us | crf_nbest k=4 us | "
              "crf_nbest k=8 us | nbest/viterbi k=4, k=8 |",
-             "|---|---|---|---|---|---|---|---|---|---|---|"]
+             "|---|---|---|---|---|---|---|---|---|---|---|---|"]
     print(torch.cuda.get_device_name(0), flush=True)
     for B, L, T in SHAPES:
         em = torch.randn(B, L, T, device="cuda")
@@ -137,7 +137,11 @@ def main():
 
             rfwd = windows(ref_step, 2, 3, 1)
             rvit = windows(ref_dec, 2, 3, 1)
-        row = (f"| {B} | {L} | {T} | {fmt(fwd)} | {fmt(rfwd)} | {fmt(vit)} | "
+        route = "n/a"   # a build without the query has the former routes
+        if hasattr(ext, "crf_fwd_route"):
+            pair, waves, lds = ext.crf_fwd_route(L, T)
+            route = f"pair {waves}w {lds} B" if pair else "wide"
+        row = (f"| {B} | {L} | {T} | {route} | {fmt(fwd)} | {fmt(rfwd)} | {fmt(vit)} | "
                f"{fmt(rvit)} | {fmt(post)} | {fmt(nb[4])} | {fmt(nb[8])} | "
                f"{ratio} |")
         print(row, flush=True)

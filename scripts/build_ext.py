@@ -16,7 +16,7 @@ CSRC = os.path.join(REPO, "csrc")
 OUT_DIR = os.path.join(REPO, "chinesener_amd", "ops")
 BUILD = os.path.join(REPO, "build")
 
-HIP_SOURCES = ["elementwise.hip", "crf.hip", "crf_wide.hip", "crf_posterior.hip",
+HIP_SOURCES = ["elementwise.hip", "crf.hip", "crf_pair.hip", "crf_wide.hip", "crf_posterior.hip",
                "crf_nbest.hip", "crf_partial.hip", "crf_constrained.hip",
                "softlexicon.hip", "adam.hip",
                "attention.hip", "attention_tiled.hip", "tener.hip", "lstm.hip", "probe.hip",
